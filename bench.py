@@ -7,7 +7,13 @@ at 22.05 kHz / hop 256 (the metric's rate; --vocoder 24k gives the JSUT recipe's
 A "step" = token ids resident on the GPU -> mel -> waveform resident on the GPU (+ one RCCL
 all-gather of int16 PCM when N > 1).  Weak scaling: every rank synthesises its own 64 utterances.
 
-Prints ONE JSON line (rank 0):
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs W untimed and K timed steps and prints ONE JSON line (rank 0) with the
+headline figures (`value`, `ms_per_step`, `dtype`, `rtf`, `stage_ms`, and the `roofline` of the fused-unit family from the HIP events of the timed
+steps, without the live ceiling and traffic figures); `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
+Everything below that takes runs of its own (other arithmetics, sizes and configs, the live MFMA ceiling, rocprofv3 passes, the CPU baseline,
+bench_detail.json) runs with `--full` only.
+
+`--full` prints ONE JSON line (rank 0):
   * headline (`value`, `ms_per_step`, `dtype`, `roofline`): the f32-EQUIVALENT emulated arithmetic `fp32_bf16x3` (VERDICT r5's ruling; DESIGN.md
     section 4): f32 tensors, every conv / fused-unit operand carried exactly as three bf16 terms, seven MFMA products per product, f32 accumulate;
     attention, normalisations and the duration predictor exact f32.  `roofline.peak` = the dense bf16 spec peak / 7; `roofline.practical_peak` =
@@ -66,6 +72,12 @@ def parse():
                     help="arithmetic of the headline numbers: fp32_bf16x3 = f32-equivalent emulated operands (three exact bf16 terms, seven MFMA products; "
                          "VERDICT r5 ruled it eligible), fp32 = exact f32 MFMA (always reported beside it as exact_f32_mode)")
     ap.add_argument("--vocoder", default="22k", choices=["22k", "24k"])
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other arithmetics, the ragged / 24 kHz / B = 1 / config / training legs, the live MFMA ceiling, "
+                         "the rocprofv3 traffic passes, the CPU baseline and bench_detail.json (the --no-* options below prune this run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "< 64 MB in all (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ragged", action="store_true", help="skip the ragged-length leg (T_text ~ U{64..t_text}, SURVEY 8d's optional variant)")
     ap.add_argument("--ragged-min", type=int, default=64, help="shortest utterance of the ragged leg, phonemes")
@@ -423,7 +435,8 @@ def run_timed(job, a, world, dist, pipeline=False, record=True, job_samples=None
     stages = ({nme: sum(e[i].elapsed_time(e[i + 1]) for e in stage_ev) / len(stage_ev)
                for i, nme in enumerate(["text2mel", "vocoder", "audio_all_gather"])} if stage_ev else None)
     return dict(dt=dt, value=total_samples / dt, ms_per_step=dt / a.steps * 1e3, rtf=dt / (total_samples / job.sr),
-                stages=stages, recs=recs, rank_ms=rank_ms, mel=r["feat_gen"], wave=y, frames=sum(r["olens"]), samples_per_step=total_samples // a.steps)
+                stages=stages, recs=recs, rank_ms=rank_ms, mel=r["feat_gen"], wave=y, frames=sum(r["olens"]), samples_per_step=total_samples // a.steps,
+                last=r, lens=lens)
 
 
 def ragged_leg(job, a, world, dist, rank, uniform_value, record=True):
@@ -849,6 +862,49 @@ DTYPE_NAME = {"fp32": "f32", "fp16": "f16 MFMA operands, f32 accumulate",
                             "f32 accumulate; attention, normalisations and the duration predictor exact f32"}
 
 
+DUMP_BUDGET = 60_000_000     # bytes of one --dump-outputs directory, all arrays together
+DUMP_SMALL = 1 << 20          # arrays of at most this many elements are always written whole
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: numpy array} -> DIR/<name>.npy.  Arrays of at most DUMP_SMALL elements are written whole; the larger ones share what
+    is left of DUMP_BUDGET, smallest first, and one that does not fit its share is written as DIR/<name>_sample.npy: its flattened elements at the
+    indices numpy.random.default_rng(0).choice(size, k, replace=False), sorted -- the same indices for every run of the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    large = sorted((v.nbytes, n) for n, v in arrays.items() if v.size > DUMP_SMALL)
+    left = DUMP_BUDGET - sum(v.nbytes for v in arrays.values() if v.size <= DUMP_SMALL)
+    for i, (nbytes, name) in enumerate(large):
+        share = left // (len(large) - i)
+        v = arrays[name]
+        if nbytes > share:
+            k = share // v.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(v.size, k, replace=False))
+            arrays.pop(name)
+            name, v = name + "_sample", v.reshape(-1)[idx]
+            arrays[name] = v
+        left -= v.nbytes
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return sorted(arrays)
+
+
+def step_outputs(head):
+    """What the timed step returned in its last step (text2mel's dict, the packed waveform, the per-utterance sample counts) as float32 arrays;
+    integer results (durations, lengths) as float64."""
+    import numpy as np
+    r = head["last"]
+    out = {"mel": r["feat_gen"], "mel_before_postnet": r.get("before"), "wave": head["wave"],
+           "pitch": r.get("pitch"), "energy": r.get("energy"), "log_duration": r.get("log_duration")}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items() if v is not None}
+    for k in ("duration", "duration_used"):
+        if r.get(k) is not None:
+            arrays[k] = r[k].detach().cpu().numpy().astype(np.float64)
+    arrays["mel_lengths"] = np.asarray(r["olens"], dtype=np.float64)
+    arrays["wave_lengths"] = np.asarray(head["lens"], dtype=np.float64)
+    return arrays
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` without a launcher: run the driver's own launch line
     (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`) as a
@@ -887,22 +943,22 @@ def main():
     if world != a.gpus:
         raise SystemExit(f"bench.py --gpus {a.gpus} launched with WORLD_SIZE={world}: --nproc-per-node must equal --gpus")
 
-    # roofline.traffic and b1_latency.kernel_ms: rocprofv3 passes run as children BEFORE this process touches the GPU
-    traffic_table = traffic_source = None
+    # roofline.traffic and b1_latency.kernel_ms (--full): rocprofv3 passes run as children BEFORE this process touches the GPU
+    traffic_table, traffic_source = None, "not measured: a plain run times the headline only (bench.py --full)"
     b1_trace = b1_trace_note = None
     special = a.pmc_child or a.b1_child or a.only_ragged or a.only_24k or a.profile_config
     tail = ["--vocoder", a.vocoder, "--batch", str(a.batch), "--t-text", str(a.t_text), "--frames-per-token", str(a.frames_per_token),
             "--precision", a.precision]
-    if rank == 0 and world == 1 and not a.no_pmc and not special:
+    if rank == 0 and world == 1 and a.full and not a.no_pmc and not special:
         n_prec = len(PRECISIONS) if a.pmc_all else len({a.precision, "fp32"})
         traffic_table, traffic_source = pmc_passes(tail + (["--pmc-all"] if a.pmc_all else []), timeout_s=120 + 60 * n_prec)
         if traffic_table is None:
             note = traffic_source
             traffic_table, traffic_source = committed_traffic()
             traffic_source = f"{traffic_source} [live passes unavailable: {note}]"
-    elif rank == 0 and not special:
+    elif rank == 0 and a.full and not special:
         traffic_table, traffic_source = committed_traffic()
-    if rank == 0 and world == 1 and not a.no_b1 and not special:
+    if rank == 0 and world == 1 and a.full and not a.no_b1 and not special:
         b1_trace, b1_trace_note = b1_trace_pass(tail + ["--b1-iters", str(a.b1_iters)])
 
     if world > 1:      # N launch-heavy host loops on one node: keep each rank's CPU-side torch work on one thread (torchrun's default too)
@@ -951,11 +1007,14 @@ def main():
         return
     # the matrix pipe's practical ceiling on THIS part, measured before any timed region (~1 s in all)
     ceilings = None
-    if not a.no_ceiling:
+    if a.full and not a.no_ceiling:
         from jatts_amd import hip as _h
         ceilings = measure_ceilings(dev, PRECISIONS if world == 1 else (a.precision, "fp32"))
         del _h
     head = run_timed(job, a, world, dist, a.pipeline)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_outputs(head))
+    head.pop("last")
     rep = kernel_report(head["recs"], a.steps, a.precision, head["dt"], traffic_table, traffic_source, ceilings)
 
     out = {
@@ -978,12 +1037,12 @@ def main():
     out.update(rep)
 
     # ---- the ragged-length leg, same arithmetic as the headline
-    if not a.no_ragged:
+    if a.full and not a.no_ragged:
         out["ragged"] = ragged_leg(job, a, world, dist, rank, out["value"])
         out["ragged"]["resunit_ms_per_step_uniform"] = rep["resunit_ms_per_step"]
 
     # ---- the other arithmetics on the same batch, and how far apart their outputs are from the headline's
-    if not a.no_fast_mode:
+    if a.full and not a.no_fast_mode:
         mel0, wav0 = head["mel"].float().clone(), head["wave"].float().clone()
         # exact f32 always rides along (exact_f32_mode); the other arithmetics at N == 1 only
         others = [p for p in PRECISIONS if p != a.precision and (world == 1 or p == "fp32")]
@@ -1014,7 +1073,7 @@ def main():
 
     # ---- the 24 kHz / hop-300 generator every JSUT / JVS recipe loads (conf/fastspeech2.v1.yaml:4-6,96-99; SURVEY 8d "report both"): the same
     # batch and acoustic model, headline arithmetic and exact f32, N == 1 only
-    if world == 1 and not a.no_24k and a.vocoder == "22k":
+    if world == 1 and a.full and not a.no_24k and a.vocoder == "22k":
         job.use_vocoder("24k")
         blk = {"sampling_rate": job.sr, "hop": job.hop, "upsample_scales": list(job.vp["upsample_scales"]),
                "workload": f"{job.name}+HiFi-GAN v1 24k (scales 5,5,4,3), {a.batch} utts x {a.t_text} phonemes x {a.frames_per_token} frames"}
@@ -1032,7 +1091,7 @@ def main():
         job.use_vocoder(a.vocoder)
 
     # ---- the drop-in B = 1 path: one utterance through model.inference(x) + vocoder.decode(mel), hipGraph replay against eager launches
-    if world == 1 and not a.no_b1:
+    if world == 1 and a.full and not a.no_b1:
         j1 = None
         g = b1_run(a, dev, a.precision, a.b1_iters, graph=True)
         j1 = g.pop("job")
@@ -1054,7 +1113,7 @@ def main():
     torch.cuda.empty_cache()
 
     # ---- BASELINE configs 3 and 5 (per-GPU share), f32 and f16: N == 1 only
-    if world == 1 and not a.no_configs:
+    if world == 1 and a.full and not a.no_configs:
         cfgs = []
         aa = argparse.Namespace(**vars(a))
         aa.steps, aa.warmup = max(2, min(3, a.steps)), 1
@@ -1095,7 +1154,7 @@ def main():
                                "8 GPUs (bench.py --gpus 8); configs[4] = 8 x the VITS line's per-GPU share")
 
     # ---- one FastSpeech2 `_train_step` at the recipe's batch size (not part of `value`): N == 1 only
-    if world == 1 and not a.no_train:
+    if world == 1 and a.full and not a.no_train:
         import gc
         out["training"] = []
         for kind in ("fs2", "matcha", "matcha_mas", "vits"):
@@ -1108,7 +1167,7 @@ def main():
             ln["fp32_split"] = {k: sp[k] for k in ("ms_per_step", "ms_per_step_mean", "loss_first", "loss_last", "dtype")}
             out["training"].append(ln)
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         from jatts_amd.synthetic import synth_texts
         total = os.cpu_count() or 1
         texts = synth_texts(a.batch, a.cpu_t_text, 45, seed=1)
@@ -1133,12 +1192,13 @@ def main():
                 out[k]["speedup_vs_cpu_rtf"] = cb["rtf"] / out[k]["rtf"]
     else:
         out["cpu_baseline"] = None
-        out["cpu_baseline_note"] = ("N=1 only (rank 0 at N=1 times the CPU leg; the N>1 line also carries no live PMC traffic: "
+        out["cpu_baseline_note"] = ("bench.py --full only" if not a.full else
+                                    "N=1 only (rank 0 at N=1 times the CPU leg; the N>1 line also carries no live PMC traffic: "
                                     "roofline.traffic is the committed table)" if world > 1 else "--no-cpu-baseline")
     if rank == 0:
         sys.stdout.flush()
         sys.stderr.flush()
-        print(compact_line(out, None if a.no_detail else write_detail(out)), flush=True)
+        print(compact_line(out, None if a.no_detail or not a.full else write_detail(out)), flush=True)
     if dist:
         dist.destroy_process_group()
 

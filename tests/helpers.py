@@ -28,6 +28,35 @@ def maxdiff(a, b):
     return float((a - b).abs().max()) if a.numel() else 0.0
 
 
+# The golden vectors were captured on an AVX-512 Intel host, where ATen, MKL and oneDNN run their AVX-512 kernels; on such a CPU the oracles
+# reproduce them within the bounds the tests state (bit for bit at the bench length).  Where those libraries take narrower vector paths
+# (another vendor, no AVX-512, or a path forced by environment) they sum f32 in another order: forcing the AVX2 and SSE paths on the capture
+# host moves the oracle outputs by up to 6.5e-5 of their magnitude, so there the bound is REORDER_RTOL x max|ref| when that is larger.
+REORDER_RTOL = 2e-4
+
+
+def _on_capture_paths():
+    if any(os.environ.get(k) for k in ("ATEN_CPU_CAPABILITY", "MKL_ENABLE_INSTRUCTIONS", "MKL_CBWR", "MKL_DEBUG_CPU_TYPE", "DNNL_MAX_CPU_ISA",
+                                       "ONEDNN_MAX_CPU_ISA")):
+        return False
+    try:
+        intel = any(ln.startswith("vendor_id") and "GenuineIntel" in ln for ln in open("/proc/cpuinfo"))
+    except OSError:
+        intel = False
+    return intel and torch.backends.cpu.get_cpu_capability() == "AVX512"
+
+
+ON_CAPTURE_PATHS = _on_capture_paths()
+
+
+def golden_bound(tol, ref):
+    """The bound an oracle output is held to against the golden vector `ref`: `tol` on the capture host's kernel paths, else the f32
+    reordering bound where that is larger (see REORDER_RTOL)."""
+    if ON_CAPTURE_PATHS:
+        return tol
+    return max(tol, REORDER_RTOL * float(np.abs(np.asarray(ref, dtype=np.float64)).max()))
+
+
 def relerr(a, b):
     a = torch.as_tensor(a).double().cpu()
     b = torch.as_tensor(b).double().cpu()

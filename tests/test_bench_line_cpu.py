@@ -103,3 +103,39 @@ def test_traffic_lookup_answers_null_with_a_reason():
     v, why = bench.lookup_traffic({"some_other_kernel": {"hbm_bytes": 1.0, "launches": 1}}, "fp32_bf16x3", 128)
     assert v is None and "resunit_emul16_kernel" in why
     assert bench.lookup_traffic(None, "fp32", 128) == (None, "no traffic table")
+
+
+def test_dump_outputs_stays_in_budget_and_samples_the_same_elements(tmp_path):
+    """--dump-outputs: small arrays whole, the large ones share the byte budget smallest first; an array that does not fit its share is written as a
+    fixed, seeded sample of its flattened elements under <name>_sample -- the same elements on every call."""
+    import numpy as np
+    g = np.random.default_rng(5)
+    arrays = lambda: {"mel": g.standard_normal((64 * 768, 80), dtype=np.float32), "wave": g.standard_normal(64 * 768 * 256, dtype=np.float32),
+                      "mel_lengths": np.full(64, 768.0)}
+    first = arrays()
+    names = bench.dump_outputs(str(tmp_path / "a"), dict(first))
+    assert names == ["mel", "mel_lengths", "wave_sample"]
+    total = sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in names)
+    assert total <= 64e6, total
+    mel, lens, wave = (np.load(tmp_path / "a" / f"{n}.npy") for n in names)
+    assert mel.dtype == np.float32 and np.array_equal(mel, first["mel"]) and lens.dtype == np.float64 and np.array_equal(lens, first["mel_lengths"])
+    assert wave.dtype == np.float32 and 5e6 < wave.size < first["wave"].size and np.isin(wave, first["wave"]).all()
+    bench.dump_outputs(str(tmp_path / "b"), dict(first))
+    assert np.array_equal(np.load(tmp_path / "b" / "wave_sample.npy"), wave)
+    small = {"mel": first["mel"][:768], "wave": first["wave"][:768 * 256]}
+    assert bench.dump_outputs(str(tmp_path / "c"), dict(small)) == ["mel", "wave"]
+
+
+def test_plain_run_options():
+    """A plain run times the headline only; --full turns the other legs on, --dump-outputs names a directory."""
+    import sys
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = bench.parse()
+        assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+        sys.argv += ["--full", "--dump-outputs", "out"]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == "out"
+    finally:
+        sys.argv = argv

@@ -86,7 +86,7 @@ def test_bench_two_ranks_on_the_shared_gpu(cuda, lib, plain):
     s.close()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, JATTS_BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "8", "--no-fast-mode"]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "8", "--no-fast-mode", "--full"]
     if plain:    # `python bench.py --gpus 2` with no launcher in the environment: bench.py starts its own two ranks as children
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import golden_state, load_golden, maxdiff
+from helpers import golden_bound, golden_state, load_golden, maxdiff
 from oracle import fs2_oracle as O
 from oracle import hifigan_oracle as HO
 from oracle import lr_oracle as LR
@@ -21,16 +21,16 @@ def test_fs2_oracle_matches_reference(name, seed, heads):
         taps = {}
         o = O.fs2_inference(sd, text, heads, alpha=alpha, taps=taps)
         assert np.array_equal(o["duration"].numpy(), z[f"u{u}_duration"])
-        # same torch build + same thread-independent kernels: bit-exact here; 1e-5 leaves room for BLAS threading
-        assert maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= 1e-5
-        assert maxdiff(o["pitch"], z[f"u{u}_pitch"]) <= 1e-5
-        assert maxdiff(o["energy"], z[f"u{u}_energy"]) <= 1e-5
+        # same torch build + same thread-independent kernels: bit-exact here; 1e-5 leaves room for BLAS threading (other CPUs: golden_bound)
+        assert maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= golden_bound(1e-5, z[f"u{u}_feat_gen"])
+        assert maxdiff(o["pitch"], z[f"u{u}_pitch"]) <= golden_bound(1e-5, z[f"u{u}_pitch"])
+        assert maxdiff(o["energy"], z[f"u{u}_energy"]) <= golden_bound(1e-5, z[f"u{u}_energy"])
         if f"u{u}_encoder_out" in z.files:
-            assert maxdiff(taps["encoder_out"], z[f"u{u}_encoder_out"]) <= 1e-5
-            assert maxdiff(taps["layer0"], z[f"u{u}_enc_layer0"]) <= 1e-5
-            assert maxdiff(taps["decoder_out"], z[f"u{u}_decoder_out"]) <= 1e-5
-            assert maxdiff(o["before"], z[f"u{u}_before"]) <= 1e-5
-            assert maxdiff(o["log_duration"], z[f"u{u}_log_duration"].reshape(-1)) <= 1e-5
+            assert maxdiff(taps["encoder_out"], z[f"u{u}_encoder_out"]) <= golden_bound(1e-5, z[f"u{u}_encoder_out"])
+            assert maxdiff(taps["layer0"], z[f"u{u}_enc_layer0"]) <= golden_bound(1e-5, z[f"u{u}_enc_layer0"])
+            assert maxdiff(taps["decoder_out"], z[f"u{u}_decoder_out"]) <= golden_bound(1e-5, z[f"u{u}_decoder_out"])
+            assert maxdiff(o["before"], z[f"u{u}_before"]) <= golden_bound(1e-5, z[f"u{u}_before"])
+            assert maxdiff(o["log_duration"], z[f"u{u}_log_duration"].reshape(-1)) <= golden_bound(1e-5, z[f"u{u}_log_duration"].reshape(-1))
         u += 1
     assert u >= 2
 
@@ -41,7 +41,7 @@ def test_fs2_oracle_speaker_embedding():
     for u in range(2):
         o = O.fs2_inference(sd, torch.tensor(z[f"u{u}_text"]), 2, spembs=torch.tensor(z[f"u{u}_spemb"]))
         assert np.array_equal(o["duration"].numpy(), z[f"u{u}_duration"])
-        assert maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= 1e-5
+        assert maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= golden_bound(1e-5, z[f"u{u}_feat_gen"])
 
 
 def test_vits_oracle_matches_reference():
@@ -55,7 +55,7 @@ def test_vits_oracle_matches_reference():
         o = vits_inference(sd, torch.tensor(z[f"u{u}_text"]), 2, 2, torch.tensor(z[f"u{u}_spemb"]),
                            torch.tensor(z[f"u{u}_noise"]))
         assert np.array_equal(o["duration"].numpy(), z[f"u{u}_duration"])
-        assert maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= 1e-5
+        assert maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= golden_bound(1e-5, z[f"u{u}_feat_gen"])
     # new rel_shift == the diagonal index map the HIP kernel uses
     bd = torch.randn(2, 5, 9)
     want = torch.stack([torch.stack([bd[:, i, 4 - i + j] for j in range(5)], -1) for i in range(5)], 1)
@@ -73,7 +73,7 @@ def test_matcha_oracle_matches_reference():
         o = matcha_inference(sd, torch.tensor(z[f"u{u}_text"]), 2, 2, torch.tensor(z[f"u{u}_noise"]),
                              n_timesteps=int(z["n_timesteps"]), temperature=float(z["temperature"]))
         assert np.array_equal(o["duration"].numpy(), z[f"u{u}_duration"])
-        assert maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= 1e-5
+        assert maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= golden_bound(1e-5, z[f"u{u}_feat_gen"])
 
 
 def test_oracles_match_reference_at_full_width():
@@ -85,17 +85,17 @@ def test_oracles_match_reference_at_full_width():
     z, keys = load_golden("matcha_jsut.npz")
     o = matcha_inference(matcha_golden_tweaks(golden_state(keys, 0)), torch.tensor(z["u0_text"]), 2, 2, torch.tensor(z["u0_noise"]),
                          n_timesteps=int(z["n_timesteps"]), temperature=float(z["temperature"]))
-    assert np.array_equal(o["duration"].numpy(), z["u0_duration"]) and maxdiff(o["feat_gen"], z["u0_feat_gen"]) <= 1e-4
+    assert np.array_equal(o["duration"].numpy(), z["u0_duration"]) and maxdiff(o["feat_gen"], z["u0_feat_gen"]) <= golden_bound(1e-4, z["u0_feat_gen"])
     z, keys = load_golden("vits_jsut.npz")
     sd = golden_state(keys, 0)
     for u in range(2):
         o = vits_inference(sd, torch.tensor(z[f"u{u}_text"]), 2, 2, torch.tensor(z[f"u{u}_spemb"]), torch.tensor(z[f"u{u}_noise"]))
-        assert np.array_equal(o["duration"].numpy(), z[f"u{u}_duration"]) and maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= 1e-4
+        assert np.array_equal(o["duration"].numpy(), z[f"u{u}_duration"]) and maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= golden_bound(1e-4, z[f"u{u}_feat_gen"])
     z, keys = load_golden("matcha_tts1_small.npz")
     sd = matcha_golden_tweaks(golden_state(keys, 4))
     for u in range(2):
         o = matcha_inference(sd, torch.tensor(z[f"u{u}_text"]), 2, 2, torch.tensor(z[f"u{u}_noise"]), n_timesteps=4, hard_lr=True)
-        assert np.array_equal(o["duration"].numpy(), z[f"u{u}_duration"]) and maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= 1e-4
+        assert np.array_equal(o["duration"].numpy(), z[f"u{u}_duration"]) and maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= golden_bound(1e-4, z[f"u{u}_feat_gen"])
 
 
 def test_rel_shift_closed_form_equals_view_trick():
@@ -254,14 +254,14 @@ def test_oracles_match_reference_at_the_bench_length():
     z, keys = load_golden("fs2_bench768.npz")
     sd = pin_duration_head(golden_state(keys, 0), 6)
     o = O.fs2_inference(sd, torch.tensor(z["u1_text"]), 2)
-    assert o["feat_gen"].shape == (768, 80) and maxdiff(o["feat_gen"], z["u1_feat_gen"]) == 0.0
+    assert o["feat_gen"].shape == (768, 80) and maxdiff(o["feat_gen"], z["u1_feat_gen"]) <= golden_bound(0.0, z["u1_feat_gen"])
     assert np.array_equal(o["duration"].numpy(), z["u1_duration"])
     z, keys = load_golden("vits_bench128.npz")
     o = vits_inference(pin_duration_head(golden_state(keys, 0), 6), torch.tensor(z["u0_text"]), 2, 2, torch.tensor(z["u0_spemb"]), noise_of(z))
-    assert o["feat_gen"].shape == (768, 80) and maxdiff(o["feat_gen"], z["u0_feat_gen"]) <= 1e-5
+    assert o["feat_gen"].shape == (768, 80) and maxdiff(o["feat_gen"], z["u0_feat_gen"]) <= golden_bound(1e-5, z["u0_feat_gen"])
     assert np.array_equal(o["duration"].numpy(), z["u0_duration"])
     z, keys = load_golden("matcha_bench128.npz")
     o = matcha_inference(pin_duration_head(matcha_golden_tweaks(golden_state(keys, 0)), 6), torch.tensor(z["u0_text"]), 2, 2, noise_of(z),
                          n_timesteps=10, temperature=0.667)
-    assert o["feat_gen"].shape == (768, 80) and maxdiff(o["feat_gen"], z["u0_feat_gen"]) <= 1e-5
+    assert o["feat_gen"].shape == (768, 80) and maxdiff(o["feat_gen"], z["u0_feat_gen"]) <= golden_bound(1e-5, z["u0_feat_gen"])
     assert np.array_equal(o["duration"].numpy(), z["u0_duration"])
