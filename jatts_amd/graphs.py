@@ -11,7 +11,11 @@ with that signature: the same kernels in the same order on the same arithmetic, 
 Rules (the trainer's graph mode follows the same ones, jatts_amd/training.py):
   * a signature's FIRST sight runs eagerly -- it fills the bounded host-to-device caches (ragged geometry, positional tables) that a
     capture may not upload into -- its SECOND sight captures, later ones replay;
-  * every cached device tensor handed out during a capture is pinned by the graph's record (hip.keep_begin), the caches may evict;
+  * every cached device tensor handed out during a capture is pinned by the graph's record (hip.keep_begin), the caches may evict.  Only
+    those: a tensor the caller looked up BEFORE the call is not recorded and is freed under the graph once the bounded caches drop it, so
+    a captured function builds its own ragged geometry from the lengths (RaggedBatch(lens, dev) inside `fn`: a cache hit, recorded);
+  * the key holds everything the launch sequence and its cached operands depend on -- besides the shapes, the positional table length of
+    the conformer stacks (ConformerRunner.table_len), which regrows for good after a longer input and changes the table's values;
   * inputs are copied into the graph's static buffers (stream-ordered), outputs are handed out as stream-ordered CLONES: a caller who
     keeps the mel of utterance n while utterance n + 1 replays the same graph sees its own values;
   * a failed capture marks the signature eager-only (logged): it never retries, and the call is answered by eager launches;

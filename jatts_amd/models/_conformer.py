@@ -154,6 +154,11 @@ class ConformerRunner:
         self.pe_len = PE_TABLE_LEN   # sticky, like the reference's regrown buffer (extend_pe)
         self._pos_cache = {}         # cap -> per-layer (per-head packed P, cv)
 
+    def table_len(self, t_max):
+        """Length of the positional table a run over t_max positions uses: the values of the legacy table depend on it, so it belongs to the
+        signature of a captured graph (a graph captured before a regrowth holds the old tables)."""
+        return max(self.pe_len, t_max)
+
     # -- positional projections: P_l = linear_pos_l(pe[:cap]); batch independent, cached per cap
     def _pos(self, t_max):
         if t_max > self.pe_len:  # positional_encoding.py:36-43: table regrown, values change

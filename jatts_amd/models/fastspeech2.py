@@ -247,8 +247,9 @@ class FastSpeech2(torch.nn.Module):
             raise ValueError("spembs required (spk_embed_dim is set)")
         sp = None if self.spk_embed_dim is None else spembs.to(dev).float().reshape(rb.n_seq, -1).contiguous()
         sd = None if self.spks is None else sids.to(dev).view(-1).long().contiguous()
-        # B = 1 (the reference's own call shape, tts_decode.py:230): both halves replay as hipGraphs keyed by (T_text) / (T_text, T_feats)
-        # (jatts_amd/graphs.py: first sight eager, second captures; bit-identical to the eager launches)
+        # B = 1 (the reference's own call shape, tts_decode.py:230): both halves replay as hipGraphs keyed by (T_text) / (T_text, T_feats) and
+        # the positional table length of the stack each half runs (jatts_amd/graphs.py: first sight eager, second captures; bit-identical to
+        # the eager launches).  The captured functions build their own geometry: a capture pins only what it was handed inside the capture
         gc = None
         if rb.n_seq == 1 and taps is None:
             gc = P.get("graphs")
@@ -261,18 +262,19 @@ class FastSpeech2(torch.nn.Module):
             sp_ = next(it) if sp is not None else None
             sd_ = next(it) if sd is not None else None
             do_ = next(it) if d_over is not None else None
-            return self._front(P, rb, ids_, sp_, sd_, do_, alpha, taps)
+            return self._front(P, hip.RaggedBatch(lens, dev), ids_, sp_, sd_, do_, alpha, None)
 
         if gc is not None:
-            hs, p_outs, e_outs, logd, d_pred, d_eff, cum, sizes = gc.run(("front", lens[0], float(alpha), sp is not None, sd is not None, d_over is not None),
-                                                                         front, (ids,) + extra)
+            hs, p_outs, e_outs, logd, d_pred, d_eff, cum, sizes = gc.run(("front", lens[0], float(alpha), sp is not None, sd is not None, d_over is not None,
+                                                                          P["enc"].table_len(lens[0])), front, (ids,) + extra)
         else:
-            hs, p_outs, e_outs, logd, d_pred, d_eff, cum, sizes = front(ids, *extra)
+            hs, p_outs, e_outs, logd, d_pred, d_eff, cum, sizes = self._front(P, rb, ids, sp, sd, d_over, alpha, taps)
         # length regulator (length_regulator.py:70-97): the one host sync of the path — output sizes
         olens_h = hip.lr_sizes_host(rb, sizes, True)    # an all-zero utterance gets all ones, as the reference's B=1 call
         rbo = hip.RaggedBatch(olens_h, dev)
         if gc is not None:
-            after, before = gc.run(("back", lens[0], olens_h[0]), lambda hs_, cum_: self._back(P, rb, rbo, hs_, cum_, None), (hs, cum))
+            after, before = gc.run(("back", lens[0], olens_h[0], P["dec"].table_len(olens_h[0])),
+                                   lambda hs_, cum_: self._back(P, hip.RaggedBatch(lens, dev), hip.RaggedBatch(olens_h, dev), hs_, cum_, None), (hs, cum))
         else:
             after, before = self._back(P, rb, rbo, hs, cum, taps)
         return dict(feat_gen=after, before=before, olens=olens_h, feats_rb=rbo, text_rb=rb, duration=d_pred,

@@ -250,9 +250,10 @@ class HiFiGANGenerator(torch.nn.Module):
                 gc = P["graphs"] = GraphCache()
             affine = tuple(t for t in (scale, shift) if t is not None)
 
-            def body(mel_, *aff):
+            def body(mel_, *aff):       # the geometry is rebuilt inside: a capture pins only the cached tensors handed out during it
                 it = iter(aff)
-                return self._generate(P, rb, mel_, next(it) if scale is not None else None, next(it) if shift is not None else None, None)
+                return self._generate(P, hip.RaggedBatch(rb.lens, rb.device), mel_, next(it) if scale is not None else None,
+                                      next(it) if shift is not None else None, None)
             return gc.run(("generate", rb.total, scale is not None, shift is not None), body, (mel,) + affine)
         return self._generate(P, rb, mel, scale, shift, taps)
 

@@ -169,11 +169,14 @@ def conformer_layer(x, pos_emb, p, n_heads, taps=None):
     return x
 
 
-def conformer_stack(x, p, n_heads, taps=None):
-    """encoder.py:233-289 after the input layer: x*sqrt(d), layers, after_norm."""
+def conformer_stack(x, p, n_heads, taps=None, table_len=PE_TABLE_LEN):
+    """encoder.py:233-289 after the input layer: x*sqrt(d), layers, after_norm.
+
+    ``table_len``: the length of the stack's positional table before this call (the reference regrows it for good, so a
+    stack that has once seen a longer input keeps the longer table)."""
     T, A = x.shape
     x = x * math.sqrt(A)
-    pos_emb = legacy_rel_pos_table(T, A, x.dtype)
+    pos_emb = legacy_rel_pos_table(T, A, x.dtype, table_len)
     for i in range(p.count("encoders")):
         lt = {} if (taps is not None and i == 0) else None
         x = conformer_layer(x, pos_emb, p.sub(f"encoders.{i}."), n_heads, lt)
@@ -238,16 +241,18 @@ def postnet(x, p):
 
 
 def fs2_inference(sd, text, n_heads, spembs=None, sids=None, alpha=1.0,
-                  durations=None, taps=None):
+                  durations=None, taps=None, enc_table_len=PE_TABLE_LEN, dec_table_len=PE_TABLE_LEN):
     """FastSpeech2.inference (fastspeech2.py:655-735), predicted d/p/e.
 
     ``durations`` (optional LongTensor) overrides the predicted durations (used
     to decouple the bit-exact length-regulator check from exp/round ulps, H3).
+    ``enc_table_len`` / ``dec_table_len``: the encoder's / decoder's positional table length left by the model's
+    earlier calls (default: a fresh model's 5000; a model that has run a longer input keeps the longer table).
     Returns dict(feat_gen, before, duration, pitch, energy, log_duration).
     """
     p = Sub(sd)
     emb = sd["encoder.embed.0.weight"][text]  # (T, A)
-    hs = conformer_stack(emb, p.sub("encoder."), n_heads, taps)
+    hs = conformer_stack(emb, p.sub("encoder."), n_heads, taps, enc_table_len)
     if taps is not None:
         taps["encoder_out"] = hs
     if sids is not None and "sid_emb.weight" in sd:
@@ -270,7 +275,7 @@ def fs2_inference(sd, text, n_heads, spembs=None, sids=None, alpha=1.0,
     if taps is not None:
         taps["variance_out"] = hs
     hs, d_eff = length_regulate(hs, d_used, alpha)
-    zs = conformer_stack(hs, p.sub("decoder."), n_heads)
+    zs = conformer_stack(hs, p.sub("decoder."), n_heads, table_len=dec_table_len)
     if taps is not None:
         taps["decoder_out"] = zs
     before = F.linear(zs, sd["feat_out.weight"], sd["feat_out.bias"])

@@ -44,6 +44,31 @@ def test_fs2_oracle_speaker_embedding():
         assert maxdiff(o["feat_gen"], z[f"u{u}_feat_gen"]) <= golden_bound(1e-5, z[f"u{u}_feat_gen"])
 
 
+def test_fs2_oracle_follows_the_regrown_positional_table():
+    """fs2_pe_regrow_small.npz (make_golden_pe_regrow.py): ONE reference model answers a short utterance, a teacher-forced call of more
+    than 5000 frames (its decoder regrows the legacy positional table for good, positional_encoding.py:36-57), then the short utterance
+    again.  The oracle reproduces both short answers -- the second with the decoder's table at the long call's length -- and the two
+    differ by orders of magnitude more than any tolerance of the suite, so a model that forgets the regrowth cannot pass for one that
+    keeps it.  (The trainers build a fresh table per step, models/fastspeech2_train.py: they do not carry it between calls.)"""
+    z, keys = load_golden("fs2_pe_regrow_small.npz")
+    sd = golden_state(keys, 0)
+    T_long = int(z["long_t_feats"])
+    assert T_long == int(z["long_durations"].sum()) > O.PE_TABLE_LEN and len(z["long_text"]) < O.PE_TABLE_LEN
+    text = torch.tensor(z["u_text"])
+    for p, dec_len in (("a", O.PE_TABLE_LEN), ("b", T_long)):
+        o = O.fs2_inference(sd, text, 2, dec_table_len=dec_len)
+        assert np.array_equal(o["duration"].numpy(), z[f"{p}_duration"])
+        for k in ("feat_gen", "pitch", "energy"):
+            assert maxdiff(o[k], z[f"{p}_{k}"]) <= golden_bound(1e-5, z[f"{p}_{k}"]), (p, k)
+    # the encoder never saw more than 5000 tokens: its table (and so pitch / energy / durations) is unchanged
+    for k in ("duration", "pitch", "energy"):
+        assert np.array_equal(z[f"a_{k}"], z[f"b_{k}"]), k
+    assert maxdiff(z["a_feat_gen"], z["b_feat_gen"]) > 50 * 2e-3      # 2e-3: the GPU suite's fp32 mel bound (tests/test_fs2_gpu.py)
+    # without the regrowth the oracle reproduces the first answer, not the second
+    o = O.fs2_inference(sd, text, 2)
+    assert maxdiff(o["feat_gen"], z["b_feat_gen"]) > 50 * 2e-3
+
+
 def test_vits_oracle_matches_reference():
     """mel-VITS (A16): oracle vs the real reference with injected noise (tests/golden/vits_small.npz)."""
     import json
