@@ -186,10 +186,7 @@ extern "C" int jatts_mas_viterbi(const jatts_ragged* rg_feats, const int32_t* cu
   const size_t W = (max_text_len + 63) / 64;
   const size_t lds = (size_t)rg_feats->max_len * W * 8 + 2 * (size_t)(max_text_len + 1) * 8 + (size_t)max_text_len * 4 + (size_t)rg_feats->max_len * 4 + 16;
   if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "mas_viterbi: T_feats x T_text decision bits exceed 160 KiB of LDS");
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)mas_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return jatts_set_error(e, __FILE__, __LINE__);
-  }
+  JATTS_RAISE_LDS_LIMIT(mas_kernel);
   hipLaunchKernelGGL(mas_kernel, dim3((unsigned)rg_feats->n_seq), dim3(256), lds, (hipStream_t)stream, *rg_feats, cu_text, log_p, ld, path, dur, score);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
@@ -203,10 +200,7 @@ extern "C" int jatts_alignment_logp(const jatts_ragged* rg_feats, const int32_t*
     return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "alignment_logp: text length must be 1..512 and <= ld");
   const size_t lds = ((size_t)max_text_len * (AL_CC + 1) + (size_t)AL_FB * (AL_CC + 1) + (size_t)AL_FB * max_text_len) * sizeof(float);
   if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "alignment_logp: text too long for LDS");
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)align_logp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return jatts_set_error(e, __FILE__, __LINE__);
-  }
+  JATTS_RAISE_LDS_LIMIT(align_logp_kernel);
   dim3 grid((unsigned)((rg_feats->max_len + AL_FB - 1) / AL_FB), (unsigned)rg_feats->n_seq);
   hipLaunchKernelGGL(align_logp_kernel, grid, dim3(256), lds, (hipStream_t)stream, *rg_feats, cu_text, feats, text, adim, log_p, ld);
   JATTS_CHECK_LAUNCH();

@@ -622,31 +622,29 @@ int launch_attn_kb(const jatts_relattn_desc& d, hipStream_t s) {
   if (total >= ((int64_t)1 << 31) - 8) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "relpos_attention: more than 2^31 query blocks (split the batch)");
   dim3 grid((unsigned)(8 * ((total + 7) / 8)));    // 1-D, decoded in XCD-aware order by the kernel
   auto kern = relattn_kernel<T, DK, KBT, REL, NW>;
-  // the dynamic-LDS limit ONCE per kernel (function-local static of this template instantiation), not per launch: the per-launch call was seen to stall the
-  // host for ~20 ms now and then (profiles/r06_notes.md section 8)
-  static const hipError_t lds_attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (lds_attr != hipSuccess) return jatts_set_error(lds_attr, __FILE__, __LINE__);
+  JATTS_RAISE_LDS_LIMIT(kern);
   hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, s, d);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
 template <typename T, int DK>
 int launch_attn(const jatts_relattn_desc& d, hipStream_t s) {
+  // f32 / split operands at d_k >= 128: 32-key tiles, two workgroups per CU (FastSpeech2 text2mel 39.8 -> 37.4 ms: profiles/r03_notes.md)
   if constexpr (sizeof(T) == 4 && DK >= 128 && DK % 64 == 0) {
-    static const int half = [] { const char* e = getenv("JATTS_ATTN_KB32"); return e ? atoi(e) : 1; }();
     // d_k 256: the split arithmetic takes 512-thread workgroups (half the hi / lo conversion work per wave, the whole next tile pair
     // prefetched: T = 768 511 -> 466 us); exact f32 is slower that way (738 -> 771 us: eight waves in lockstep on the barriers) and
-    // keeps four waves with half a tile in flight.  JATTS_ATTN_NW8 = 0 / 1 forces either (tools/ A/B only).
-    static const int wide = [] { const char* e = getenv("JATTS_ATTN_NW8"); return e ? atoi(e) : -1; }();
-    if constexpr (DK == 256 && sizeof(typename G<T>::type) == 4) {
-      if (half && (wide >= 0 ? wide != 0 : G<T>::split)) return launch_attn_kb<T, DK, 32, true, 8>(d, s);
+    // keeps four waves with half a tile in flight.
+    if constexpr (DK == 256 && G<T>::split) {
+      return launch_attn_kb<T, DK, 32, true, 8>(d, s);
+    } else {
+      if constexpr (DK == 256) {
+        if (!d.g && !d.ku) return launch_attn_kb<T, DK, 32, false>(d, s);
+      }
+      return launch_attn_kb<T, DK, 32>(d, s);
     }
-    if constexpr (DK == 256 && sizeof(typename G<T>::type) == 4 && !G<T>::split) {
-      if (half && !d.g && !d.ku) return launch_attn_kb<T, DK, 32, false>(d, s);
-    }
-    if (half) return launch_attn_kb<T, DK, 32>(d, s);
+  } else {
+    return launch_attn_kb<T, DK, KB>(d, s);
   }
-  return launch_attn_kb<T, DK, KB>(d, s);
 }
 
 template <typename T>

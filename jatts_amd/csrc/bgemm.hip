@@ -7,8 +7,6 @@
 // One workgroup = 4 waves = a 128 x 128 (or 128 x 64) tile of C (each wave 64 x 64 = 2 x 2 fragments, or 64 x 32); K runs in chunks of 32
 // through a double-buffered LDS pair As[k][m], Bs[k][n] (pitch 132: the transposing store of a K-contiguous operand hits 64 distinct
 // banks); the loads of chunk i + 1 are issued before the MFMAs of chunk i.  A fragment operand is one ds_read_b32 per lane and K-pair.
-#include <stdlib.h>
-
 #include "common.h"
 
 #ifndef JATTS_BGEMM_DIAG
@@ -228,8 +226,6 @@ extern "C" int jatts_bgemm(const float* a, int64_t sa_outer, int64_t sa_inner, i
   const int n_batch = n_outer * n_inner;
   auto launch = [&](auto kern, int bn, int bk, int bm) -> int {
     const int lds = 2 * bk * (bm + 4 + bn + 4) * (int)sizeof(float);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-      return jatts_set_error_msg(JATTS_ERR_HIP, "bgemm: could not raise the dynamic LDS limit");
     g.n_batch = n_batch;
     g.gx = (n + bn - 1) / bn;
     g.gy = (m + bm - 1) / bm;
@@ -244,7 +240,12 @@ extern "C" int jatts_bgemm(const float* a, int64_t sa_outer, int64_t sa_inner, i
                    ((sa_outer | sa_inner | sb_outer | sb_inner | (int64_t)lda | (int64_t)ldb) & 3) == 0;
   const int tile = (n > 128 && n <= 192) ? 3 : (n64 * 4 <= n128 * 3 ? 1 : 2);
   int rc = JATTS_ERR_UNSUPPORTED;
-#define JATTS_BGEMM_CASE(WNF, BKC_, AKv, BKv, VECv, MFv) rc = launch(bgemm_kernel<WNF, BKC_, AKv, BKv, VECv, MFv>, 64 * WNF, BKC_, 64 * MFv)
+  // (the dynamic-LDS limit is raised here, not in the lambda: a static there would be one for every kernel of this signature)
+#define JATTS_BGEMM_CASE(WNF, BKC_, AKv, BKv, VECv, MFv)                                 \
+  do {                                                                                   \
+    JATTS_RAISE_LDS_LIMIT((bgemm_kernel<WNF, BKC_, AKv, BKv, VECv, MFv>));               \
+    rc = launch(bgemm_kernel<WNF, BKC_, AKv, BKv, VECv, MFv>, 64 * WNF, BKC_, 64 * MFv); \
+  } while (0)
 #define JATTS_BGEMM_ORIENT(WNF, BKC_, VECv, MFv)                                         \
   do {                                                                                   \
     if (!trans_a && trans_b) JATTS_BGEMM_CASE(WNF, BKC_, true, true, VECv, MFv);         \
@@ -252,10 +253,9 @@ extern "C" int jatts_bgemm(const float* a, int64_t sa_outer, int64_t sa_inner, i
     else if (trans_a && !trans_b) JATTS_BGEMM_CASE(WNF, BKC_, false, false, VECv, MFv);  \
     else JATTS_BGEMM_CASE(WNF, BKC_, false, true, VECv, MFv);                            \
   } while (0)
-  // 64-row tiles when the 128-row tiling leaves fewer than two rounds of the 512 two-per-CU slots (see bgemm_kernel); JATTS_BGEMM_MF = 1 / 2 forces either
-  static const int mf_env = [] { const char* e = getenv("JATTS_BGEMM_MF"); return e ? atoi(e) : 0; }();
+  // 64-row tiles when the 128-row tiling leaves fewer than two rounds of the 512 two-per-CU slots (see bgemm_kernel)
   const int64_t wg128 = (int64_t)n_batch * ((m + 127) / 128) * ((n + 191) / 192);
-  const bool half_m = mf_env ? mf_env == 1 : (m > 64 && wg128 < 1024);
+  const bool half_m = m > 64 && wg128 < 1024;
   if (!vec && tile == 3) JATTS_BGEMM_ORIENT(3, 16, false, 1);     // (n = d_k = 192 in one 64 x 192 tile here too: the T x T operand is read once)
   else if (!vec) JATTS_BGEMM_ORIENT(2, 16, false, 2);            // element loads: any alignment (a padded batch length T % 4 != 0 takes it for P v and its gradients)
   else if (tile == 3 && half_m) JATTS_BGEMM_ORIENT(3, 16, true, 1);

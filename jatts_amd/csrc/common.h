@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "../../include/jatts_hip.h"
 
 typedef _Float16 f16;
@@ -24,6 +26,31 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 int jatts_set_error(hipError_t e, const char* file, int line);
 int jatts_set_error_msg(int code, const char* msg);
+
+// A kernel's dynamic-LDS limit raised to the CU's whole 160 KiB (less the kernel's static __shared__), ONCE per kernel and device rather than per launch:
+// the per-launch call was seen to stall the host for ~20 ms now and then (profiles/r06_notes.md section 8).  `done` holds one bit per device (devices
+// beyond 63 are not cached) and is set only on success, so a failed call is tried again at the next launch.
+inline hipError_t jatts_raise_lds_limit(std::atomic<uint64_t>& done, const void* kern) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const uint64_t bit = dev < 64 ? (uint64_t)1 << dev : 0;
+  if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
+  hipFuncAttributes fa;
+  e = hipFuncGetAttributes(&fa, kern);
+  if (e == hipSuccess) e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes);
+  if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
+  return e;
+}
+
+// The cache is a static of the CALL SITE: in a launcher templated on the tile, one per kernel instantiation.  (A static of a helper templated on the
+// kernel's type would be shared: every instantiation of a kernel template has the same function type.)
+#define JATTS_RAISE_LDS_LIMIT(kern)                                                 \
+  do {                                                                              \
+    static std::atomic<uint64_t> lds_done_{0};                                      \
+    const hipError_t e_ = jatts_raise_lds_limit(lds_done_, (const void*)(kern));    \
+    if (e_ != hipSuccess) return jatts_set_error(e_, __FILE__, __LINE__);           \
+  } while (0)
 
 // ---------------------------------------------------------------- element traits
 template <typename T> struct Elem;

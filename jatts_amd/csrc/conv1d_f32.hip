@@ -1,14 +1,10 @@
 // jatts_conv1d, f32 operands (v_mfma_f32_32x32x2_f32: exact f32 fma chains, the reference's arithmetic).
-#include <stdlib.h>
-
 #include "conv1d_impl.h"
 
 int jatts_conv1d_f32_direct(const jatts_conv_desc& d, int variant, hipStream_t s);   // conv1d_f32_direct.hip
 
 int jatts_conv1d_f32(const jatts_conv_desc& d, hipStream_t s) {
-  // JATTS_CONV_F32_TILE (process-wide tuning override) / jatts_conv_desc.variant (per call): see include/jatts_hip.h
-  static const int env_tile = [] { const char* e = getenv("JATTS_CONV_F32_TILE"); return e ? atoi(e) : 0; }();
-  const int tile = d.variant ? d.variant : env_tile;
+  const int tile = d.variant;   // jatts_conv_desc.variant forces a tile (per call): see include/jatts_hip.h
   // default: the register-streamed kernel wherever it applies (one plain zero-padded input: every projection / FFN / postnet conv of the
   // acoustic models): 2-20 % faster than the LDS-staged tiles on every shape of tools/bench_conv.py (profiles/r03_notes.md)
   if (tile == 0 || tile >= 3) {

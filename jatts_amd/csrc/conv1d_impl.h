@@ -311,10 +311,7 @@ int launch_conv_k(const jatts_conv_desc& d, hipStream_t s) {
   }
   if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d: halo too large for LDS");
   auto kern = conv1d_kernel<T, NF, NT, WN, WT, NIN, ASYNC, KCHT>;
-  // the dynamic-LDS limit ONCE per kernel (function-local static of this template instantiation), not per launch: the per-launch call was seen to stall the
-  // host for ~20 ms now and then (profiles/r06_notes.md section 8)
-  static const hipError_t lds_attr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (lds_attr != hipSuccess) return jatts_set_error(lds_attr, __FILE__, __LINE__);
+  JATTS_RAISE_LDS_LIMIT(kern);
   XcdOrder xo;
   const int64_t total = xo.plan((int)grid.x, (int)grid.y, (int)grid.z, (int64_t)BN * d.c_in * d.k_w * (int64_t)sizeof(T), ragged_tiles_1d(d.rg, BT));
   if (total >= (int64_t)1 << 31) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d: launch too large");
@@ -330,8 +327,7 @@ int launch_conv(const jatts_conv_desc& d, hipStream_t s) {
   if constexpr (sizeof(T) == 2 && NF == 2 && NT == 2 && WN == 2) {
     // 128-channel chunks for deep-K convs: half as many stage -> barrier -> MFMA round trips per workgroup (a k=1
     // projection with K=384 is otherwise 6 latency-bound chunk iterations around 2 us of MFMA work)
-    static const int kch = [] { const char* e = getenv("JATTS_CONV_KCH"); return e ? atoi(e) : 2; }();  // 0: never, 1: k=1 only, 2: all (default)
-    if (small_halo && d.n_in == 1 && d.c_in % 128 == 0 && d.c_in >= 256 && (kch == 2 || (kch == 1 && d.k_w == 1)))
+    if (small_halo && d.n_in == 1 && d.c_in % 128 == 0 && d.c_in >= 256)
       return launch_conv_k<T, NF, NT, WN, WT, 1, true, 128>(d, s);
   }
   if (small_halo && multi_chunk && d.n_in == 1) return launch_conv_k<T, NF, NT, WN, WT, 1, true>(d, s);

@@ -1,8 +1,6 @@
 // HBM-bound row-wise kernels of the jatts hot path (gfx950): embedding, LayerNorm,
 // affine/cast, conformer GLU+depthwise+BN+Swish, predictor heads, variance embeddings,
 // length regulator (bit-exact integer path), Gaussian upsampling, HiFi-GAN output conv.
-#include <stdlib.h>
-
 #include "common.h"
 
 namespace {
@@ -967,8 +965,7 @@ extern "C" int jatts_groupnorm_mish(const jatts_ragged* rg, const void* x, int32
   if (workspace && (gc & 7) == 0 && GN_TCH * gc <= 256 * GN_MAXU * 8) {   // time-split two-launch form
     const int n_chunks = (rg->max_len + GN_TCH - 1) / GN_TCH;
     dim3 grid3((unsigned)groups, (unsigned)rg->n_seq, (unsigned)n_chunks), blk3(256);
-    static const int rows_env = [] { const char* e = getenv("JATTS_GN_ROWS"); return e ? atoi(e) : 1; }();
-    const bool rows_form = rows_env && groups <= GN_MAXG && (channels & 7) == 0;
+    const bool rows_form = groups <= GN_MAXG && (channels & 7) == 0;
 #define GN2_GO(TI, TO)                                                                                                   \
   do {                                                                                                                   \
     hipLaunchKernelGGL((gn_partial_kernel<TI>), grid3, blk3, 0, S_, *rg, (const TI*)x, channels, groups, workspace, n_chunks); \

@@ -2,8 +2,6 @@
 // gradients of jatts_conv1d.  The data gradient of a conv is jatts_conv1d itself on flipped, transposed weights.
 // Reference: jatts/trainers/fastspeech2.py:24-100 (_train_step), jatts/losses/{l1l2_loss,duration_predictor_loss,
 // variance_predictor_loss}.py, torch.nn.Conv1d's autograd.
-#include <stdlib.h>
-
 #include "common.h"
 #include "det_reduce.h"
 
@@ -416,14 +414,12 @@ extern "C" int jatts_conv1d_wgrad(const jatts_ragged* rg, const float* x, int32_
   int groups = (1024 + tiles - 1) / tiles;            // enough workgroups to fill the chip; each group strides over the sequences
   if (groups > rg->n_seq) groups = rg->n_seq;
   if (groups < 1) groups = 1;
-  static const int use_mfma = [] { const char* e = getenv("JATTS_WGRAD_MFMA"); return e ? atoi(e) : 1; }();
-  if (use_mfma && (k_w == 1 || k_w == 3 || k_w == 5) && (k_w - 1) * dil <= 32) {
+  if ((k_w == 1 || k_w == 3 || k_w == 5) && (k_w - 1) * dil <= 32) {
     const int tiles_m = ((n_out + 63) / 64) * ((c_in + 63) / 64);
     // Sequence groups (split-K factor): the launch ends when the fullest CU has walked its workgroups, each over ceil(n_seq / g) sequences
     // -- minimise ceil(tiles g / 256) ceil(n_seq / g) (the old "at least 1 536 workgroups" rule gave 1 584 for 1536 x 384: 7 on some CUs, 6
-    // on others, each 3 sequences long = 21 units against 18 for g = 16: 840 -> 782 us; tools/sweep_wgrad_groups.sh), preferring four resident
+    // on others, each 3 sequences long = 21 units against 18 for g = 16: 840 -> 782 us), preferring four resident
     // workgroups per CU, with a small tax per group for the reduction pass.  Deterministic: a function of the shapes only.
-    static const int g_env = [] { const char* e = getenv("JATTS_WGRAD_GROUPS"); return e ? atoi(e) : 0; }();   // (tools/ A/B only)
     int g = 1;
     {
       double best = 1e300;
@@ -437,9 +433,6 @@ extern "C" int jatts_conv1d_wgrad(const jatts_ragged* rg, const float* x, int32_
         if (cost < best) { best = cost; g = c; }
       }
     }
-    if (g_env > 0) g = g_env;
-    if (g > rg->n_seq) g = rg->n_seq;
-    if (g < 1) g = 1;
     const dim3 grid((unsigned)((n_out + 63) / 64), (unsigned)((c_in + 63) / 64), (unsigned)g);
     const size_t lds = 2 * (size_t)(64 + (k_w - 1) * dil) * 68 * sizeof(float);   // two buffers of (dy tile | x tile + halo)
     // bias partials live behind the weight partials: workspace[g k n64 c64 ..][g][n64]

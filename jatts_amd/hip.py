@@ -7,7 +7,6 @@ descriptor and launches asynchronously on ``torch.cuda.current_stream()``.
 import collections
 import contextlib
 import ctypes as C
-import os
 
 import torch
 
@@ -339,8 +338,8 @@ class RaggedBatch:
         return self._vt
 
 
-# 1-D grids over the real tiles of a ragged batch (jatts_ragged.total_rows); JATTS_RAGGED_1D=0: the rectangular grids (A/B runs)
-_RAGGED_1D = os.environ.get("JATTS_RAGGED_1D", "1") != "0"
+# 1-D grids over the real tiles of a ragged batch (jatts_ragged.total_rows); False: the rectangular grids (tests compare the two)
+_RAGGED_1D = True
 
 
 def round_up(v, m):
@@ -431,10 +430,6 @@ def pack_conv_weight_bf16x3_k32(w, c_mult=64):
     return pack_unit_weight_bf16x3_k32(wp)
 
 
-# fragment order of the emulated convs' weights: "16" = the v_mfma_f32_16x16x32_bf16 kernels (round 6), "32" = the round-5 32 x 32 x 16 kernels (A/B runs)
-CONV_EMUL_FORM = os.environ.get("JATTS_CONV_EMUL_FORM", "16")
-
-
 class SplitWeight:
     """A conv weight prepared for JATTS_F32S (the pair of pack_conv_weight_split).  hip.conv1d recognises it in place of a packed f32
     weight -- call sites stay `dtype=hip.F32` -- and takes the split kernel; shapes the split kernel does not cover (a halo beyond 32
@@ -457,7 +452,7 @@ class EmulWeight:
 
     def __init__(self, w, c_mult=64, code=F32E, layout=None):
         self.code = code
-        self.layout = (1 if CONV_EMUL_FORM == "16" and c_mult % 64 == 0 else 0) if layout is None else layout      # jatts_conv_desc.w_layout
+        self.layout = (1 if c_mult % 64 == 0 else 0) if layout is None else layout      # jatts_conv_desc.w_layout
         self.packed = pack_conv_weight_bf16x3_k32(w, c_mult) if self.layout else pack_conv_weight_bf16x3(w, c_mult)
         self._src, self._c_mult, self._f32 = w.detach(), c_mult, None
 

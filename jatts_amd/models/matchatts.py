@@ -22,7 +22,7 @@ import torch
 from .. import hip
 from ..hip import ACT_MISH, ACT_NONE, ACT_RELU, ACT_SWISH
 from . import _schema as S
-from ._conformer import QKV_ONE_LAUNCH, ConformerRunner, PackedConv, SpkProjection
+from ._conformer import ConformerRunner, PackedConv, SpkProjection
 from .fastspeech2 import _Predictor
 
 GN_EPS = 1e-5  # torch.nn.GroupNorm / LayerNorm defaults (decoder.py:71, transformer.py:213)
@@ -96,10 +96,14 @@ class _TBlock:
         self.dh = self.inner // heads
         if self.dh % 32:
             raise NotImplementedError("attention head dim must be a multiple of 32")
-        self.qk = PackedConv(torch.cat([wq, wk], 0), None, dt, dev)
-        self.v = PackedConv(sd[p + "attn1.to_v.weight"], None, dt, dev)
-        # Q | K | V as ONE launch (jatts_conv_desc.n_split; transformer.py:222-260 issues three Linear calls): Q | K row-major, V transposed
-        self.qkv = PackedConv(torch.cat([wq, wk, sd[p + "attn1.to_v.weight"]], 0), None, dt, dev) if (2 * self.inner) % 256 == 0 else None
+        # Q | K | V as ONE launch (jatts_conv_desc.n_split; transformer.py:222-260 issues three Linear calls): Q | K row-major, V transposed;
+        # Q | K and V as two launches where the Q | K width is not whole 256-wide tiles
+        self.qkv = self.qk = self.v = None
+        if (2 * self.inner) % 256 == 0:
+            self.qkv = PackedConv(torch.cat([wq, wk, sd[p + "attn1.to_v.weight"]], 0), None, dt, dev)
+        else:
+            self.qk = PackedConv(torch.cat([wq, wk], 0), None, dt, dev)
+            self.v = PackedConv(sd[p + "attn1.to_v.weight"], None, dt, dev)
         self.o = PackedConv(sd[p + "attn1.to_out.0.weight"], sd[p + "attn1.to_out.0.bias"], dt, dev)
         self.ff1 = PackedConv(sd[p + "ff.net.0.proj.weight"], sd[p + "ff.net.0.proj.bias"], dt, dev)
         self.ff2 = PackedConv(sd[p + "ff.net.2.weight"], sd[p + "ff.net.2.bias"], dt, dev)
@@ -112,7 +116,7 @@ class _TBlock:
         C, I = x.shape[1], self.inner
         n = hip.layernorm(x, self.n1[0], self.n1[1], dt, GN_EPS)
         vcol, ldvt = rb.vt_layout()
-        if self.qkv is not None and QKV_ONE_LAUNCH:
+        if self.qkv is not None:
             qk, vt = hip.conv1d(rb, n, self.qkv.w, self.qkv.c_in, 3 * I, 1, dtype=dt, split=(2 * I, ldvt, vcol))
         else:
             qk = hip.conv1d(rb, n, self.qk.w, self.qk.c_in, 2 * I, 1, dtype=dt)

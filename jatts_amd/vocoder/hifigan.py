@@ -11,8 +11,6 @@ Kernel schedule per batch: affine/cast -> input conv (MFMA implicit GEMM) -> per
 upsample stage [polyphase ConvTranspose as MFMA conv (LeakyReLU + MRF mean fused on the
 input side) -> 3 ResBlocks x 3 fused dilation units] -> output conv + tanh.
 """
-import contextlib
-import os
 
 import torch
 
@@ -29,11 +27,6 @@ class PackedSplitConv:
         self.n_out, self.c_in, self.k = w.shape
         self.w, self.inv = hip.pack_conv_weight_split(w, 32)
         self.b = b.detach().float().contiguous()
-
-
-# fragment order of the emulated units' weights: "16" = the v_mfma_f32_16x16x32_bf16 kernels (round 6: the power-limited matrix pipe sustains 14 % more of that
-# form, csrc/resunit_emul16_impl.h), "32" = the round-5 v_mfma_f32_32x32x16_bf16 kernels (A/B runs; the fused ResBlock launches always take them)
-EMUL_UNIT_FORM = os.environ.get("JATTS_RESUNIT_EMUL_FORM", "16")
 
 
 class PackedEmulConv:
@@ -195,7 +188,9 @@ class HiFiGANGenerator(torch.nn.Module):
                 units = []
                 for di, d in enumerate(self.resblock_dilations[j]):
                     q = f"blocks.{i * nb + j}."
-                    k32 = EMUL_UNIT_FORM == "16" and c_out % 32 == 0
+                    # the units' weights in the fragment order of the v_mfma_f32_16x16x32_bf16 kernels (round 6: the power-limited matrix pipe sustains
+                    # 14 % more of that form, csrc/resunit_emul16_impl.h); the fused ResBlock launches take the 32 x 32 x 16 form (also32)
+                    k32 = c_out % 32 == 0
                     mk = (PackedSplitConv if split else (lambda w, b: PackedEmulConv(w, b, k32, (c_out, rk) in self.fused_blocks_emul)) if emul
                           else (lambda w, b: PackedConv(w, b, dt, dev, c_mult=32)))   # fused unit takes c_in == channels
                     c1 = mk(padw(sd[q + f"convs1.{di}.1.weight"], c_out, c_out).to(dev), padb(sd[q + f"convs1.{di}.1.bias"], c_out).to(dev))
@@ -211,30 +206,19 @@ class HiFiGANGenerator(torch.nn.Module):
         return P
 
     # (channels, kernel size) of the ResBlocks issued as ONE fused launch (jatts_hifigan_resblock): the shapes where it
-    # measured faster than three unit launches (profiles/r02_notes.md); JATTS_HIFIGAN_FUSE=0 switches it off
-    fused_blocks = frozenset() if os.environ.get("JATTS_HIFIGAN_FUSE", "1") == "0" else frozenset({(32, 3), (32, 7), (64, 3)})
+    # measured faster than three unit launches (profiles/r02_notes.md)
+    fused_blocks = frozenset({(32, 3), (32, 7), (64, 3)})
     # f32 (round 3): only the k = 3 block of the 32-channel stage, where a conv is 6 K-steps and the per-unit launches spend as long in their
     # staging / store phases as in their MFMAs: 4.11 vs 4.42 ms (0.72 vs 0.66 of the f32 MFMA peak).  C = 64 k = 3 measured 4 % SLOWER fused
     # (7.78 vs 7.48 ms: the 24-row chain halo of a 256-column window) and stays on the per-unit path (tools/bench_unit.py --resblock
-    # --dtype f32); JATTS_HIFIGAN_FUSE_F32=0 switches the fused launch off (A/B runs)
-    fused_blocks_f32 = frozenset() if os.environ.get("JATTS_HIFIGAN_FUSE_F32", "1") == "0" else frozenset({(32, 3)})
-    # fp32_split (round 4): the HBM-bound blocks -- x in + y out once per ResBlock (csrc/resblock_split_impl.h); JATTS_HIFIGAN_FUSE_SPLIT=0: per-unit launches
-    fused_blocks_split = (frozenset() if os.environ.get("JATTS_HIFIGAN_FUSE_SPLIT", "1") == "0"
-                          else frozenset(tuple(int(v) for v in t.split("x")) for t in os.environ.get("JATTS_HIFIGAN_FUSE_SPLIT_SET", "32x3,32x7,64x3").split(",")))
+    # --dtype f32)
+    fused_blocks_f32 = frozenset({(32, 3)})
+    # fp32_split (round 4): the HBM-bound blocks -- x in + y out once per ResBlock (csrc/resblock_split_impl.h)
+    fused_blocks_split = frozenset({(32, 3), (32, 7), (64, 3)})
 
     # fp32_bf16x3 / fp32_bf16x3_6p (round 5, csrc/resblock_emul_impl.h): only C = 32, k = 3 measured faster fused (3.60 vs 3.93 ms; C = 32 k = 7 0.82x, C = 64 k = 3 0.93-0.96x:
-    # the 6-byte tile leaves one workgroup per CU or a 72 %-useful window; profiles/r05_notes.md); JATTS_HIFIGAN_FUSE_EMUL=0: per-unit launches
-    fused_blocks_emul = (frozenset() if os.environ.get("JATTS_HIFIGAN_FUSE_EMUL", "1") == "0"
-                         else frozenset(tuple(int(v) for v in t.split("x")) for t in os.environ.get("JATTS_HIFIGAN_FUSE_EMUL_SET", "32x3").split(",")))
-
-    # tuning knob (profiles/r01_notes.md): run the independent ResBlock chains of a stage on separate HIP streams
-    concurrent = os.environ.get("JATTS_HIFIGAN_STREAMS", "0") == "1"
-
-    def _side_streams(self, n):
-        pool = self.__dict__.setdefault("_streams", [])
-        while len(pool) < n:
-            pool.append(torch.cuda.Stream())
-        return pool[:n]
+    # the 6-byte tile leaves one workgroup per CU or a 72 %-useful window; profiles/r05_notes.md)
+    fused_blocks_emul = frozenset({(32, 3)})
 
     @torch.no_grad()
     def inference_batch(self, rb, mel, scale=None, shift=None, taps=None):
@@ -242,7 +226,7 @@ class HiFiGANGenerator(torch.nn.Module):
         scale/shift: optional per-channel affine applied first (Vocoder.decode normalisation).
         Returns f32 (rows * hop,) packed waveforms (utterance b owns samples cu[b]*hop ...)."""
         P = self._prepare()
-        if rb.n_seq == 1 and taps is None and not self.concurrent:
+        if rb.n_seq == 1 and taps is None:
             # B = 1 (Vocoder.decode, the reference's call shape vocoder.py:56-67): the ~150 launches of one utterance replay as ONE hipGraph per frame
             # count (jatts_amd/graphs.py: first sight eager, second captures, bit-identical)
             gc = P.get("graphs")
@@ -277,23 +261,13 @@ class HiFiGANGenerator(torch.nn.Module):
             outs = []
             blocks = P["blocks"][i]
             fuse_mean = c_out in supported and len(blocks) in (2, 3)
-            # The ResBlocks of a stage are independent chains: with JATTS_HIFIGAN_STREAMS=1 all but the last run on
-            # side streams so that workgroups of memory-heavy (k=3) and MFMA-heavy (k=11) units share the CUs.
-            # Every buffer of the stage is allocated up front on the launch stream and held until the join.
-            side = self._side_streams(len(blocks) - 1) if (self.concurrent and c_out in supported) else []
-            main = torch.cuda.current_stream() if side else None
             bufs = [[torch.empty_like(up), torch.empty_like(up)] for _ in blocks]
-            if side:
-                fork = torch.cuda.Event()
-                fork.record(main)
-            done = []
             for j, units in enumerate(blocks):
                 cur = up
-                st = side[j] if j < len(side) else None
                 # HBM-bound shapes: the whole ResBlock in one launch (x read once, y written once; residual in registers)
                 fset = (self.fused_blocks_split if udt == hip.F32S else self.fused_blocks_emul if udt in hip.EMUL
                         else (self.fused_blocks if dt == hip.F16 else self.fused_blocks_f32))
-                if (c_out, units[0][2]) in fset and len(units) <= 3 and st is None \
+                if (c_out, units[0][2]) in fset and len(units) <= 3 \
                         and sum((units[0][2] - 1) // 2 * (u[3] + 1) for u in units) <= (64 if (dt == hip.F16 or udt == hip.F32S or udt in hip.EMUL) else 16):
                     lastb = fuse_mean and j == len(blocks) - 1
                     hip.hifigan_resblock(rb, rate, cur, bufs[j][0], [(getattr(c1, "w32", c1.w), c1.b, getattr(c2, "w32", c2.w), c2.b, d) for c1, c2, _, d in units],
@@ -302,29 +276,16 @@ class HiFiGANGenerator(torch.nn.Module):
                                          ws=[(c1.inv, c2.inv) for c1, c2, _, _ in units] if udt == hip.F32S else None)
                     outs.append(bufs[j][0])
                     continue
-                if st is not None:
-                    st.wait_event(fork)
-                with torch.cuda.stream(st) if st is not None else contextlib.nullcontext():
-                    for di, (c1, c2, rk, d) in enumerate(units):
-                        nxt = bufs[j][di & 1]
-                        # (c_out is always a fused-unit width: _prepare zero-pads narrower stages and refuses wider ones)
-                        last = fuse_mean and j == len(blocks) - 1 and di == len(units) - 1
-                        if last:
-                            for ev in done:
-                                torch.cuda.current_stream().wait_event(ev)
-                        # the last unit of the last ResBlock writes the MRF mean (cs / num_blocks) directly
-                        hip.hifigan_resunit(rb, rate, cur, nxt, c1.w, c1.b, c2.w, c2.b, c_out, rk, d, self.slope, udt,
-                                            add=outs if last else None, out_scale=1.0 / len(blocks) if last else 1.0,
-                                            ws=(c1.inv, c2.inv) if udt == hip.F32S else None, w_layout=getattr(c1, "layout", 0))
-                        cur = nxt
-                    if st is not None:
-                        ev = torch.cuda.Event()
-                        ev.record(st)
-                        done.append(ev)
+                for di, (c1, c2, rk, d) in enumerate(units):
+                    nxt = bufs[j][di & 1]
+                    # (c_out is always a fused-unit width: _prepare zero-pads narrower stages and refuses wider ones)
+                    last = fuse_mean and j == len(blocks) - 1 and di == len(units) - 1
+                    # the last unit of the last ResBlock writes the MRF mean (cs / num_blocks) directly
+                    hip.hifigan_resunit(rb, rate, cur, nxt, c1.w, c1.b, c2.w, c2.b, c_out, rk, d, self.slope, udt,
+                                        add=outs if last else None, out_scale=1.0 / len(blocks) if last else 1.0,
+                                        ws=(c1.inv, c2.inv) if udt == hip.F32S else None, w_layout=getattr(c1, "layout", 0))
+                    cur = nxt
                 outs.append(cur)
-            if side and not fuse_mean:
-                for ev in done:
-                    main.wait_event(ev)
             if fuse_mean:
                 xs, in_scale = [outs[-1]], 1.0
             else:

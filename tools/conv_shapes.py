@@ -1,9 +1,8 @@
 #!/usr/bin/env python3
 """Per-shape jatts_conv1d time inside the real workloads (live HIP events, jatts_amd.hip profile hooks): one training step of a model
-(--train fs2|matcha|matcha_mas|vits) or one inference step (--infer fs2|matcha|vits).  Run it once per JATTS_CONV_F32_TILE setting
-(unset = the product heuristic, 1 / 2 = the LDS-staged tiles, 3 = register-streamed) and diff the tables: that is how the f32 kernel
-heuristic is tuned.
-    JATTS_CONV_F32_TILE=2 python tools/conv_shapes.py --train vits"""
+(--train fs2|matcha|matcha_mas|vits) or one inference step (--infer fs2|matcha|vits), with the library's own tile choice: the shapes that
+matter to a workload, to be timed tile by tile with tools/bench_conv.py (which forces jatts_conv_desc.variant).
+    python tools/conv_shapes.py --train vits"""
 import argparse
 import collections
 import os
@@ -47,7 +46,7 @@ def main():
             agg[meta][0] += 1
             agg[meta][1] += ms
     tot = sum(v[1] for v in agg.values())
-    print(f"# JATTS_CONV_F32_TILE={os.environ.get('JATTS_CONV_F32_TILE', '(unset)')}: {len(recs)} timed launches, conv1d total {tot:.2f} ms")
+    print(f"# {len(recs)} timed launches, conv1d total {tot:.2f} ms")
     for meta, (n, ms) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:a.top]:
         c, no, k, rows = meta
         print(f"{c:5d} -> {no:5d} k={k:2d} rows={rows:7d}  x{n:3d}  {ms:8.3f} ms  {2.0 * c * no * k * rows * n / ms / 1e9:7.1f} TFLOP/s")

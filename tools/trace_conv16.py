@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Phase clocks of the emulated 16 x 16 x 32 conv (DIAG build with -DJATTS_CEMUL_TRACE=1: jatts_amd/lib_diagT, JATTS_HIP_LIB): per workgroup, the
 shader clocks wave 0 spends in each phase of the chunk loop (conv1d_emul16.h: JATTS_PH).
-    JATTS_HIP_LIB=$PWD/jatts_amd/lib_diagT/libjatts_hip.so python tools/trace_conv16.py --only 5 [--variant 2]"""
+    JATTS_HIP_LIB=$PWD/jatts_amd/lib_diagT/libjatts_hip.so python tools/trace_conv16.py --only 5"""
 import argparse
 import ctypes as C
 import os
@@ -54,7 +54,7 @@ def main():
     ph = t[:, 1:8].astype(np.float64)
     tot = (t[:, 11] - t[:, 10]).astype(np.float64)
     rt = (t[:, 9] - t[:, 8]).astype(np.float64)
-    print(f"{c} -> {n} k={k} rows={rows} variant {os.environ.get('JATTS_CONV_EMUL16_VARIANT', '0')}: launch {ms * 1e3:.1f} us = "
+    print(f"{c} -> {n} k={k} rows={rows} (product tile): launch {ms * 1e3:.1f} us = "
           f"{2.0 * c * n * k * rows / ms / 1e9:.1f} TFLOP/s (traced build), {len(t)} workgroups on {len(np.unique(cu))} CUs")
     print(f"  workgroup lifetime: mean {tot.mean():9.0f} clk, median {np.median(tot):9.0f}; shader clock {np.mean(tot / (rt * 10.0)):.3f} GHz (s_memtime / s_memrealtime)")
     for i, nme in enumerate(PH):
