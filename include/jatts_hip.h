@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define JATTS_ABI_VERSION 4   /* 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
+#define JATTS_ABI_VERSION 5   /* 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
                                 * so every descriptor that embeds it (jatts_conv_desc, jatts_resunit_desc, jatts_resblock_desc, jatts_relattn_desc) shifted by 8 bytes; JATTS_F32E; 2 (round 4): jatts_conv_desc + w_inv / act_a / act_b, jatts_resunit_desc + ws1 / ws2, jatts_resblock_desc + ws1 / ws2;
                                 * bumped whenever a descriptor's layout or an entry point's signature changes: a stale library is refused at load */
 
@@ -203,9 +203,18 @@ typedef struct jatts_resunit_desc {
    * order of jatts_conv_weight_index (v_mfma_f32_32x32x16_bf16 kernels).  1: [tap][c / 32][n / 16][lane = 16 ((c % 32) / 8) + n % 16][c % 8] x (b0 | b1 | b2)
    * (v_mfma_f32_16x16x32_bf16 kernels, csrc/resunit_emul16_impl.h: the form the power-limited matrix pipe sustains 14 % more of; jatts_unit_weight_index_k32). */
   int32_t w_layout;
+  /* (ABI 5) 0: the library picks the form (the product setting).  Non-zero forces one where it applies (the w_layout = 1 emulated units; parity tests,
+   * tools/bench_unit.py): 1 = WINDOWED, one workgroup per window of columns, each recomputing the k - 1 halo columns of the inner activation and
+   * discarding k - 1 outputs; 2 = SLIDING, one workgroup per CU slot walking a run of consecutive windows that carries the halo from window to window
+   * (csrc/resunit_emul16_impl.h).  Bit-identical results.  Unknown / inapplicable values fall back to 0's choice or to the windowed form. */
+  int32_t variant;
 } jatts_resunit_desc;
 
 int jatts_hifigan_resunit(const jatts_resunit_desc* d, void* stream);
+
+/* The form jatts_hifigan_resunit would launch for d on the current device: 1 = windowed, 2 = sliding (jatts_resunit_desc.variant), or a negative
+ * error code.  Launches nothing. */
+int jatts_resunit_variant(const jatts_resunit_desc* d);
 
 /* Index of W[n][tap][c] (one of the three bf16 planes' 8-element groups counted as one element) inside a w_layout = 1 buffer (HOST helper, pure function). */
 int64_t jatts_unit_weight_index_k32(int32_t n, int32_t tap, int32_t c, int32_t channels);

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JATTS_HIP_LIB") or os.path.join(_HERE, "lib", "libjatts_hip.so")  # override: profiling builds only
 
 F32, F16, F32S, F32E, F32E6 = 0, 1, 2, 3, 4      # F32S: f32 in HBM, split f16 hi/lo MFMA operands (jatts_hifigan_resunit only)
-ABI_VERSION = 4      # JATTS_ABI_VERSION of include/jatts_hip.h (tests/test_abi_cpu.py compares the two)
+ABI_VERSION = 5      # JATTS_ABI_VERSION of include/jatts_hip.h (tests/test_abi_cpu.py compares the two)
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SWISH, ACT_MISH, ACT_SNAKEBETA = 0, 1, 2, 3, 4, 5
 PRE_NONE, PRE_LRELU = 0, 1
 PAD_ZERO, PAD_REFLECT = 0, 1
@@ -41,7 +41,7 @@ class ResUnitDesc(C.Structure):
         ("dil", C.c_int32), ("slope", C.c_float), ("x", C.c_void_p), ("y", C.c_void_p),
         ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
         ("add0", C.c_void_p), ("add1", C.c_void_p), ("out_scale", C.c_float),
-        ("ws1", C.c_void_p), ("ws2", C.c_void_p), ("w_layout", C.c_int32),
+        ("ws1", C.c_void_p), ("ws2", C.c_void_p), ("w_layout", C.c_int32), ("variant", C.c_int32),
     ]
 
 
@@ -73,6 +73,7 @@ PROTOTYPES = {
     "jatts_conv1d": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     "jatts_conv_weight_index": (C.c_int64, [C.c_int32] * 5),
     "jatts_hifigan_resunit": (C.c_int, [C.POINTER(ResUnitDesc), C.c_void_p]),
+    "jatts_resunit_variant": (C.c_int, [C.POINTER(ResUnitDesc)]),
     "jatts_unit_weight_index_k32": (C.c_int64, [C.c_int32] * 4),
     "jatts_hifigan_resblock": (C.c_int, [C.POINTER(ResBlockDesc), C.c_void_p]),
     "jatts_debug_trace": (C.c_int, [C.c_void_p, C.c_int64]),

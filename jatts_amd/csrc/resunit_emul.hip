@@ -36,26 +36,33 @@ static int resunit_emul(const jatts_resunit_desc& d, hipStream_t s) {
 }
 
 // The same tiles on v_mfma_f32_16x16x32_bf16 (w_layout = 1; resunit_emul16_impl.h): waves as (WN, WT), a wave's tile 64 channels x 64 columns wherever the
-// channel count allows (C = 32: 32 x 64, C = 64 with two workgroups per CU: 32 x 64).
+// channel count allows (C = 32: 32 x 64, C = 64 with two workgroups per CU: 32 x 64).  Each tile runs windowed or sliding (carried h halo;
+// jatts_resunit_desc.variant, resunit16_pick); `pick` non-null: report the form, launch nothing.
 template <typename T>
-static int resunit_emul16(const jatts_resunit_desc& d, hipStream_t s) {
+static int resunit_emul16(const jatts_resunit_desc& d, hipStream_t s, int* pick) {
   const int halo = (d.k_w - 1) * d.dil;
   switch (d.channels) {
     // (round 6, measured and dropped -- profiles/r06_unit16_c64_c32_wide.txt: C = 32 with 512-column windows, one workgroup per CU: 9 - 22 % slower; the
     //  one-workgroup-per-CU C = 64 unit at k = 3 / 7: 10 - 12 % / 4 % slower.  Small-channel units live on the second resident workgroup.)
-    case 32: return launch_resunit_emul16<T, 32, 256, 1, 4, 2, false, true>(d, s);
+    case 32: return launch_resunit_emul16<T, 32, 256, 1, 4, 2, false, true>(d, s, pick);
     case 64:
-      if (d.k_w >= 11) return launch_resunit_emul16<T, 64, 256, 1, 4, 1, false, true>(d, s);
-      return launch_resunit_emul16<T, 64, 128, 2, 2, 2, false, true>(d, s);
-    case 128: return launch_resunit_emul16<T, 128, 128, 2, 2, 1>(d, s);
+      if (d.k_w >= 11) return launch_resunit_emul16<T, 64, 256, 1, 4, 1, false, true>(d, s, pick);
+      return launch_resunit_emul16<T, 64, 128, 2, 2, 2, false, true>(d, s, pick);
+    case 128: return launch_resunit_emul16<T, 128, 128, 2, 2, 1>(d, s, pick);
     case 256:
-      if ((64 + halo) * 1552 + 2048 <= 160 * 1024) return launch_resunit_emul16<T, 256, 64, 4, 1, 1>(d, s);
-      return launch_resunit_emul16<T, 256, 64, 4, 1, 1, true>(d, s);
+      // the one-piece x tile where the WINDOWED form fits; the sliding form's parked tail ((k - 1) x 1536 B) fits beside it at every HiFi-GAN v1 shape
+      // (tightest: k = 11, dilation 3 -- 163 296 of 163 840 B), and a shape where it did not would stay windowed (launch_resunit_emul16)
+      if ((64 + halo) * 1552 + 2048 <= 160 * 1024) return launch_resunit_emul16<T, 256, 64, 4, 1, 1>(d, s, pick);
+      return launch_resunit_emul16<T, 256, 64, 4, 1, 1, true>(d, s, pick);
   }
   return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: unsupported channels for JATTS_F32E (32 / 64 / 128 / 256)");
 }
 
-int jatts_resunit_emul(const jatts_resunit_desc& d, hipStream_t s) {
-  if (d.w_layout == 1) return d.dtype == JATTS_F32E6 ? resunit_emul16<bf3f>(d, s) : resunit_emul16<bf3>(d, s);
+int jatts_resunit_emul(const jatts_resunit_desc& d, hipStream_t s, int* pick) {
+  if (d.w_layout == 1) return d.dtype == JATTS_F32E6 ? resunit_emul16<bf3f>(d, s, pick) : resunit_emul16<bf3>(d, s, pick);
+  if (pick) {                // the 32 x 32 x 16 kernels are windowed only
+    *pick = 1;
+    return JATTS_OK;
+  }
   return d.dtype == JATTS_F32E6 ? resunit_emul<bf3f>(d, s) : resunit_emul<bf3>(d, s);
 }

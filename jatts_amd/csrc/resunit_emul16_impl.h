@@ -184,7 +184,18 @@ __device__ __forceinline__ void conv16(typename Acc16<T>::type (&acc)[NF][NT], W
   }
 }
 
-template <typename T, int C, int WGCOLS, int WN, int WT, int OCC, bool KSPLIT = false, bool RREG = false>      // T = bf3 (seven partial products) or bf3f (six)
+// Two forms of the unit (jatts_resunit_desc.variant).  A window owns WGCOLS columns; h tile row r <-> position t0 - p2 + r in both.
+//  * WINDOWED (SLIDE = false): one workgroup per window.  conv1 over h at [t0 - p2, t0 - p2 + WGCOLS), conv2 over the same WGCOLS columns, and only
+//    tt_out = WGCOLS - (K - 1) outputs [t0, t0 + tt_out) are stored: the other K - 1 conv2 columns are discarded and the K - 1 halo columns of h are
+//    computed again by the neighbouring window -- (K - 1) / WGCOLS of the launch's MFMA work.
+//  * SLIDING (SLIDE = true, "carried halo"): gridDim.x resident workgroups, each walking a run of consecutive windows -- the batch's positions cut into
+//    gridDim.x equal pieces, located from cu_rows on the device (valid under graph replay).  A window that follows one of the same sequence keeps the
+//    last K - 1 h rows of the one before as the first K - 1 rows of its h tile (the TAIL; parked between conv2 and the next epilogue 1 in K - 1 rows of
+//    C * 6 bytes past the x / h region: the next x staging and the f32 y tile overwrite the region): conv1 computes only the WGCOLS new h columns
+//    [t0 + p2, t0 + p2 + WGCOLS) and all WGCOLS conv2 columns are stored.  The first window of a run and of every sequence it reaches is windowed;
+//    its last K - 1 h rows are exactly the next window's tail.
+// Every output column's contractions run the same taps and K-steps in the same order in both forms: the results are bit-identical.
+template <typename T, int C, int WGCOLS, int WN, int WT, int OCC, bool KSPLIT = false, bool RREG = false, bool SLIDE = false>      // T = bf3 (seven partial products) or bf3f (six)
 __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit_emul16_kernel(jatts_resunit_desc d, unsigned long long* trace, unsigned trace_cap,
                                                                          unsigned bias_off) {
   typedef typename Elem<T>::vec8 V8;
@@ -193,6 +204,7 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit_emul16_kernel(jatts_
   constexpr int KC32 = C / 32, NFR16 = C / 16;
   constexpr int pitch = C * 6 + 16;
   constexpr int pitch_x = KSPLIT ? (C / 2) * 6 + 16 : pitch;
+  constexpr int pitch_t = C * 6;     // SLIDE: the parked tail rows
   constexpr int NTHR = WN * WT * 64;
   static_assert(NF * WN * 16 == C && NT * WT * 16 == WGCOLS && C % 32 == 0, "tile shape");
   static_assert(sizeof(T) == 6, "bf3 is three packed bf16");
@@ -202,6 +214,7 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit_emul16_kernel(jatts_
   f32x8 xk[MAXI];
   const unsigned wg_lin = blockIdx.x + blockIdx.y * gridDim.x;
   const bool tracing = trace != nullptr && wg_lin < trace_cap && threadIdx.x == 0;
+  // (SLIDE: the phase stamps are those of the run's last window)
 #define JATTS_STAMP(i) do { if (tracing) trace[(size_t)wg_lin * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
   if (tracing) {
     unsigned hwid, xcc;
@@ -215,29 +228,38 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit_emul16_kernel(jatts_
   const int p2 = (K - 1) / 2, p1 = p2 * dil;
   const int tt_out = WGCOLS - 2 * p2;
 
-  int b = blockIdx.y, bx = blockIdx.x;
-  if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, tt_out, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
-  const int row_b = d.rg.cu_rows[b];
-  const int L = (d.rg.cu_rows[b + 1] - row_b) * d.rg.len_mul;
-  const int t0 = bx * tt_out;
-  if (t0 >= L) return;
-  const int64_t seq_row0 = (int64_t)row_b * d.rg.len_mul;
+  int b, t0;                     // the window: sequence, first output position
+  int64_t f_seq = 0, f_end = 0;  // SLIDE, in flat positions (rows past cu_rows[0] x len_mul): sequence b's first one, the end of this run
+  if constexpr (!SLIDE) {
+    int bx = blockIdx.x;
+    b = blockIdx.y;
+    if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, tt_out, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
+    t0 = bx * tt_out;
+  } else {
+    const int c0 = d.rg.cu_rows[0];
+    const int64_t total = (int64_t)(d.rg.cu_rows[d.rg.n_seq] - c0) * d.rg.len_mul;
+    const int64_t per = (total + gridDim.x - 1) / gridDim.x;
+    const int64_t f = (int64_t)blockIdx.x * per;
+    if (f >= total) return;
+    f_end = min(total, f + per);
+    b = find_seq(d.rg.cu_rows, d.rg.n_seq, c0 + (int)(f / d.rg.len_mul));
+    f_seq = (int64_t)(d.rg.cu_rows[b] - c0) * d.rg.len_mul;
+    t0 = (int)(f - f_seq);
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wn = wave / WT, wt = wave % WT;
   const int g4 = lane >> 4;                 // which 4 of a fragment's 16 channels this lane owns in C / D
   const int col0 = wt * NT * 16;
   const int nf0 = wn * NF;
 
-  const int rx = WGCOLS + 2 * p1;   // x tile rows: row r <-> position t0 - p2 - p1 + r
+  const int rx = WGCOLS + 2 * p1;   // x tile rows: row r <-> position t0 - p2 + off - p1 + r
   char* xs = smem;                  // bf3 lrelu(x) tile; h overlays it; finally the f32 y tile
   char* hs = smem;
   float* bs = reinterpret_cast<float*>(smem + bias_off);   // b1 | b2
+  char* tl = smem + bias_off - (SLIDE ? (K - 1) * pitch_t : 0);    // SLIDE: the parked tail, between the x / h region and the biases
   for (int u = threadIdx.x; u < 2 * C; u += NTHR) bs[u] = u < C ? d.b1[u] : d.b2[u - C];
 
   WStream16<T, NF> ws;
-  ws.bind((const T*)d.w1, KC32, NFR16, nf0, lane);
-  ws.fetch(0, 0);                  // conv1's first K-step, under the staging
-
   typename Acc16<T>::type acc[NF][NT];
   auto bias_acc = [&](const float* bv) {
 #pragma unroll
@@ -262,238 +284,316 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit_emul16_kernel(jatts_
     return o;
   };
   const float* x = (const float*)d.x;
-  const int pos0 = t0 - p2 - p1;
-  if constexpr (!KSPLIT) {
-    constexpr int UPR = C / 8;
-    constexpr int UB = 8;
-    const int total = rx * UPR;
-    if constexpr (RREG) {
-      const int r_in = p1 + p2, n_in = tt_out * UPR;
-#pragma unroll
-      for (int j = 0; j < MAXI; ++j) {
-        const int v = threadIdx.x + j * NTHR;
-        const int ro = v / UPR, cu = v - ro * UPR;
-        const int pos = t0 + ro;
-        if (v < n_in && pos < L) xk[j] = Vec8IO<float>::ldg(x + (seq_row0 + pos) * (int64_t)C + cu * 8);
-        else xk[j] = f32x8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-      const int n_halo = (rx - tt_out) * UPR;
-      for (int base = threadIdx.x; base < n_halo; base += NTHR * UB) {
-        f32x8 v[UB];
-#pragma unroll
-        for (int j = 0; j < UB; ++j) {
-          const int u = base + j * NTHR;
-          int r = u / UPR;
-          const int cu = u - r * UPR;
-          if (r >= r_in) r += tt_out;
-          const int pos = pos0 + r;
-          if (u < n_halo && pos >= 0 && pos < L) v[j] = Vec8IO<float>::ldg(x + (seq_row0 + pos) * (int64_t)C + cu * 8);
-          else v[j] = f32x8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int j = 0; j < UB; ++j) {
-          const int u = base + j * NTHR;
-          if (u >= n_halo) continue;
-          int r = u / UPR;
-          const int cu = u - r * UPR;
-          if (r >= r_in) r += tt_out;
-          Vec8IO<T>::sts(xs + (size_t)r * pitch + (size_t)cu * 48, to_planes(v[j]));
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < MAXI; ++j) {
-        const int v = threadIdx.x + j * NTHR;
-        if (v >= n_in) continue;
-        const int ro = v / UPR, cu = v - ro * UPR;
-        Vec8IO<T>::sts(xs + (size_t)(r_in + ro) * pitch + (size_t)cu * 48, to_planes(xk[j]));
-      }
-    } else {
-      // the WHOLE tile in one batch of loads (halos up to 32 rows a side; longer ones take a second pass): the accumulators are not live yet, and a second
-      // batch is a second serial HBM round trip -- 3.5 k of a C = 128 workgroup's 138 k cycles
-      constexpr int UBX = ((WGCOLS + 64) * UPR + NTHR - 1) / NTHR;
-      for (int base = threadIdx.x; base < total; base += NTHR * UBX) {
-        f32x8 v[UBX];
-#pragma unroll
-        for (int j = 0; j < UBX; ++j) {
-          const int u = base + j * NTHR;
-          const int r = u / UPR, cu = u - r * UPR;
-          const int pos = pos0 + r;
-          if (u < total && pos >= 0 && pos < L) v[j] = Vec8IO<float>::ldg(x + (seq_row0 + pos) * (int64_t)C + cu * 8);
-          else v[j] = f32x8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int j = 0; j < UBX; ++j) {
-          const int u = base + j * NTHR;
-          if (u >= total) continue;
-          const int r = u / UPR, cu = u - r * UPR;
-          Vec8IO<T>::sts(xs + (size_t)r * pitch + (size_t)cu * 48, to_planes(v[j]));
-        }
-      }
+  bool slide = false;               // this window carries the previous one's tail
+  for (bool first = true;; first = false) {
+    unsigned tid = threadIdx.x;
+    // a fresh value each window: keeps the compiler from hoisting the per-thread staging / store addresses out of the window loop, where they would
+    // stay live across both convs and spill
+    if constexpr (SLIDE) asm volatile("" : "+v"(tid));
+    const int row_b = d.rg.cu_rows[b];
+    const int L = (d.rg.cu_rows[b + 1] - row_b) * d.rg.len_mul;
+    if constexpr (!SLIDE) {
+      if (t0 >= L) return;
     }
-    __syncthreads();
-    JATTS_STAMP(2);
-    bias_acc(bs);
-    conv16<T, NF, NT, KC32>(acc, ws, 0, K, dil, xs, pitch, col0, lane, (const T*)d.w2 + (size_t)nf0 * 512 + (size_t)lane * 8);
-  } else {
-    constexpr int UPR = C / 16;                                            // 8-element units per row of one channel half
-    constexpr int MAXU = ((WGCOLS + 64) * UPR + NTHR - 1) / NTHR;         // halos up to 32 rows a side (the launcher refuses more)
-    const int total = rx * UPR;
-    f32x8 xv[MAXU];
-    auto load_half = [&](int half) {
-#pragma unroll
-      for (int j = 0; j < MAXU; ++j) {
-        const int u = threadIdx.x + j * NTHR;
-        const int r = u / UPR, cu = u - r * UPR;
-        const int pos = pos0 + r;
-        if (u < total && pos >= 0 && pos < L) xv[j] = Vec8IO<float>::ldg(x + (seq_row0 + pos) * (int64_t)C + half * (C / 2) + cu * 8);
-        else xv[j] = f32x8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-    };
-    auto store_half = [&]() {
-#pragma unroll
-      for (int j = 0; j < MAXU; ++j) {
-        const int u = threadIdx.x + j * NTHR;
-        if (u < total) Vec8IO<T>::sts(xs + (size_t)(u / UPR) * pitch_x + (size_t)(u % UPR) * 48, to_planes(xv[j]));
-      }
-    };
-    load_half(0);
-    store_half();
-    load_half(1);                 // in flight under the first half's MFMAs
-    __syncthreads();
-    JATTS_STAMP(2);
-    bias_acc(bs);
-    // first channel half: weight steps 0 .. KC32 / 2 - 1 of every tap; the stream continues with the second half's first step
-    conv16<T, NF, NT, KC32 / 2>(acc, ws, 0, K, dil, xs, pitch_x, col0, lane, ws.wl + (size_t)(KC32 / 2) * ws.kc_stride);
-    lds_barrier();                // every wave is done reading the first half
-    store_half();
-    lds_barrier();
-    conv16<T, NF, NT, KC32 / 2>(acc, ws, KC32 / 2, K, dil, xs, pitch_x, col0, lane, (const T*)d.w2 + (size_t)nf0 * 512 + (size_t)lane * 8);
-  }
-  finish_acc();
-  JATTS_STAMP(3);
-
-  // ---- epilogue 1: h = lrelu(acc), 0 outside the sequence (conv2's zero padding) -> three planes over the dead x tile
-  lds_barrier();     // every wave is done reading x (conv2's first weights stay in flight)
-  JATTS_STAMP(10);
-  for (int u = threadIdx.x; u < (K - 1) * (C / 8); u += NTHR) {   // rows past the computed columns: read by discarded columns only
-    const int r = WGCOLS + u / (C / 8), cu = u % (C / 8);
-    V8 z;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) z.b0[e] = z.b1[e] = z.b2[e] = (bf16)0.f;
-    Vec8IO<T>::sts(hs + (size_t)r * pitch + (size_t)cu * 48, z);
-  }
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int col = col0 + t * 16 + (lane & 15);
-    const int pos = t0 - p2 + col;
-    const float keep = (pos >= 0 && pos < L) ? 1.f : 0.f;
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const int n0 = (nf0 + f) * 16 + 4 * g4;       // this lane's 4 channels
-      float v[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float a = acc16_val(acc[f][t])[e] * keep;
-        v[e] = fmaxf(a, a * d.slope);
-      }
-      bf16x4 q0, q1, q2;
-      bf3_split4(v, q0, q1, q2);
-      char* p = hs + (size_t)col * pitch + (size_t)(n0 >> 3) * 48 + (size_t)(n0 & 4) * 2;
-      *reinterpret_cast<bf16x4*>(p) = q0;
-      *reinterpret_cast<bf16x4*>(p + 16) = q1;
-      *reinterpret_cast<bf16x4*>(p + 32) = q2;
+    const int64_t seq_row0 = (int64_t)row_b * d.rg.len_mul;
+    const int off = slide ? 2 * p2 : 0;               // conv1 column c -> h row c + off
+    const int nout = slide ? WGCOLS : tt_out;         // conv2 columns stored: [t0, t0 + nout)
+    int nvalid = min(nout, L - t0);
+    if constexpr (SLIDE) {
+      nvalid = (int)min((int64_t)nvalid, f_end - f_seq - t0);
+      if (!first) __syncthreads();    // every wave is done with the previous window's y tile
     }
-  }
-  JATTS_STAMP(12);
-  lds_barrier();
-  JATTS_STAMP(4);
 
-  bias_acc(bs + C);
-  ws.bind((const T*)d.w2, KC32, NFR16, nf0, lane);     // (ra already holds w2's first step)
-  conv16<T, NF, NT, KC32>(acc, ws, 0, K, 1, hs, pitch, col0, lane, nullptr);
-  finish_acc();
-  JATTS_STAMP(5);
-
-  // ---- epilogue 2: acc (+ b2, already in) assembled as an f32 tile in LDS; the residual (and the MRF mean) are added in the row-contiguous store pass
-  __syncthreads();
-  char* ys = smem;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int col = col0 + t * 16 + (lane & 15);
-    if (col >= tt_out || t0 + col >= L) continue;
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const int n0 = (nf0 + f) * 16 + 4 * g4;
-      *reinterpret_cast<f32x4*>(ys + (size_t)col * pitch + (size_t)n0 * 4) = acc16_val(acc[f][t]);
-    }
-  }
-  __syncthreads();
-  JATTS_STAMP(6);
-  {
-    const int vrows = min(tt_out, L - t0);
-    const int64_t g0 = (seq_row0 + t0) * (int64_t)C;
-    constexpr bool keep_small = C <= 64;
-    const float* xg = (const float*)d.x;
-    float* yg = (float*)d.y;
-    if constexpr (RREG) {
+    ws.bind((const T*)d.w1, KC32, NFR16, nf0, lane);
+    ws.fetch(0, 0);                  // conv1's first K-step, under the staging
+    const int pos0 = t0 - p2 + off - p1;
+    if constexpr (!KSPLIT) {
       constexpr int UPR = C / 8;
-      const int n_out = vrows * UPR;
-      const bool has_add1 = d.add0 != nullptr && d.add1 != nullptr;
-      f32x8 a0[MAXI], a1[MAXI];
-      if (d.add0) {
+      constexpr int UB = 8;
+      const int total = rx * UPR;
+      if constexpr (RREG) {
+        const int r_in = p1 + p2 - off, n_in = nout * UPR;   // x rows of the stored outputs [t0, t0 + nout)
 #pragma unroll
         for (int j = 0; j < MAXI; ++j) {
-          const int v = threadIdx.x + j * NTHR;
-          if (v < n_out) {
-            a0[j] = Vec8IO<float>::ldg((const float*)d.add0 + g0 + (int64_t)v * 8);
-            if (has_add1) a1[j] = Vec8IO<float>::ldg((const float*)d.add1 + g0 + (int64_t)v * 8);
+          const int v = tid + j * NTHR;
+          const int ro = v / UPR, cu = v - ro * UPR;
+          const int pos = t0 + ro;
+          if (v < n_in && pos < L) xk[j] = Vec8IO<float>::ldg(x + (seq_row0 + pos) * (int64_t)C + cu * 8);
+          else xk[j] = f32x8{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+        const int n_halo = (rx - nout) * UPR;
+        for (int base = tid; base < n_halo; base += NTHR * UB) {
+          f32x8 v[UB];
+#pragma unroll
+          for (int j = 0; j < UB; ++j) {
+            const int u = base + j * NTHR;
+            int r = u / UPR;
+            const int cu = u - r * UPR;
+            if (r >= r_in) r += nout;
+            const int pos = pos0 + r;
+            if (u < n_halo && pos >= 0 && pos < L) v[j] = Vec8IO<float>::ldg(x + (seq_row0 + pos) * (int64_t)C + cu * 8);
+            else v[j] = f32x8{0, 0, 0, 0, 0, 0, 0, 0};
+          }
+#pragma unroll
+          for (int j = 0; j < UB; ++j) {
+            const int u = base + j * NTHR;
+            if (u >= n_halo) continue;
+            int r = u / UPR;
+            const int cu = u - r * UPR;
+            if (r >= r_in) r += nout;
+            Vec8IO<T>::sts(xs + (size_t)r * pitch + (size_t)cu * 48, to_planes(v[j]));
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < MAXI; ++j) {
+          const int v = tid + j * NTHR;
+          if (v >= n_in) continue;
+          const int ro = v / UPR, cu = v - ro * UPR;
+          Vec8IO<T>::sts(xs + (size_t)(r_in + ro) * pitch + (size_t)cu * 48, to_planes(xk[j]));
+        }
+      } else {
+        // the WHOLE tile in one batch of loads (halos up to 32 rows a side; longer ones take a second pass): the accumulators are not live yet, and a second
+        // batch is a second serial HBM round trip -- 3.5 k of a C = 128 workgroup's 138 k cycles
+        constexpr int UBX = ((WGCOLS + 64) * UPR + NTHR - 1) / NTHR;
+        for (int base = tid; base < total; base += NTHR * UBX) {
+          f32x8 v[UBX];
+#pragma unroll
+          for (int j = 0; j < UBX; ++j) {
+            const int u = base + j * NTHR;
+            const int r = u / UPR, cu = u - r * UPR;
+            const int pos = pos0 + r;
+            if (u < total && pos >= 0 && pos < L) v[j] = Vec8IO<float>::ldg(x + (seq_row0 + pos) * (int64_t)C + cu * 8);
+            else v[j] = f32x8{0, 0, 0, 0, 0, 0, 0, 0};
+          }
+#pragma unroll
+          for (int j = 0; j < UBX; ++j) {
+            const int u = base + j * NTHR;
+            if (u >= total) continue;
+            const int r = u / UPR, cu = u - r * UPR;
+            Vec8IO<T>::sts(xs + (size_t)r * pitch + (size_t)cu * 48, to_planes(v[j]));
           }
         }
       }
+      __syncthreads();
+      JATTS_STAMP(2);
+      bias_acc(bs);
+      conv16<T, NF, NT, KC32>(acc, ws, 0, K, dil, xs, pitch, col0, lane, (const T*)d.w2 + (size_t)nf0 * 512 + (size_t)lane * 8);
+    } else {
+      constexpr int UPR = C / 16;                                            // 8-element units per row of one channel half
+      constexpr int MAXU = ((WGCOLS + 64) * UPR + NTHR - 1) / NTHR;         // halos up to 32 rows a side (the launcher refuses more)
+      const int total = rx * UPR;
+      f32x8 xv[MAXU];
+      auto load_half = [&](int half) {
 #pragma unroll
-      for (int j = 0; j < MAXI; ++j) {
-        const int v = threadIdx.x + j * NTHR;
-        if (v >= n_out) continue;
-        const int ro = v / UPR, cu = v - ro * UPR;
-        f32x8 o = Vec8IO<float>::lds(ys + (size_t)ro * pitch + (size_t)cu * 32);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = o[e] + xk[j][e];          // residual
-        if (d.add0) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = (o[e] + a0[j][e] + (has_add1 ? a1[j][e] : 0.f)) * d.out_scale;
+        for (int j = 0; j < MAXU; ++j) {
+          const int u = tid + j * NTHR;
+          const int r = u / UPR, cu = u - r * UPR;
+          const int pos = pos0 + r;
+          if (u < total && pos >= 0 && pos < L) xv[j] = Vec8IO<float>::ldg(x + (seq_row0 + pos) * (int64_t)C + half * (C / 2) + cu * 8);
+          else xv[j] = f32x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
-        float* dst = yg + g0 + (int64_t)v * 8;
-        *reinterpret_cast<f32x4*>(dst) = f32x4{o[0], o[1], o[2], o[3]};
-        *reinterpret_cast<f32x4*>(dst + 4) = f32x4{o[4], o[5], o[6], o[7]};
+      };
+      auto store_half = [&]() {
+#pragma unroll
+        for (int j = 0; j < MAXU; ++j) {
+          const int u = tid + j * NTHR;
+          if (u < total) Vec8IO<T>::sts(xs + (size_t)(u / UPR) * pitch_x + (size_t)(u % UPR) * 48, to_planes(xv[j]));
+        }
+      };
+      load_half(0);
+      store_half();
+      load_half(1);                 // in flight under the first half's MFMAs
+      __syncthreads();
+      JATTS_STAMP(2);
+      bias_acc(bs);
+      // first channel half: weight steps 0 .. KC32 / 2 - 1 of every tap; the stream continues with the second half's first step
+      conv16<T, NF, NT, KC32 / 2>(acc, ws, 0, K, dil, xs, pitch_x, col0, lane, ws.wl + (size_t)(KC32 / 2) * ws.kc_stride);
+      lds_barrier();                // every wave is done reading the first half
+      store_half();
+      lds_barrier();
+      conv16<T, NF, NT, KC32 / 2>(acc, ws, KC32 / 2, K, dil, xs, pitch_x, col0, lane, (const T*)d.w2 + (size_t)nf0 * 512 + (size_t)lane * 8);
+    }
+    finish_acc();
+    JATTS_STAMP(3);
+
+    // ---- epilogue 1: h = lrelu(acc), 0 outside the sequence (conv2's zero padding) -> three planes over the dead x tile
+    lds_barrier();     // every wave is done reading x (conv2's first weights stay in flight)
+    JATTS_STAMP(10);
+    if (SLIDE && slide) {
+      for (int u = tid; u < (K - 1) * (C / 8); u += NTHR) {   // the carried tail: h rows 0 .. K - 2
+        const int r = u / (C / 8), cu = u % (C / 8);
+        Vec8IO<T>::sts(hs + (size_t)r * pitch + (size_t)cu * 48, Vec8IO<T>::lds(tl + (size_t)r * pitch_t + (size_t)cu * 48));
       }
     } else {
-      if (d.add0) unit_store_pass<float, C, keep_small ? 2 : 4, true, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
-      else unit_store_pass<float, C, keep_small ? 4 : 8, false, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
+      for (int u = tid; u < (K - 1) * (C / 8); u += NTHR) {   // rows past the computed columns: read by discarded columns only
+        const int r = WGCOLS + u / (C / 8), cu = u % (C / 8);
+        V8 z;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) z.b0[e] = z.b1[e] = z.b2[e] = (bf16)0.f;
+        Vec8IO<T>::sts(hs + (size_t)r * pitch + (size_t)cu * 48, z);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int col = col0 + t * 16 + (lane & 15);
+      const int pos = t0 - p2 + off + col;
+      const float keep = (pos >= 0 && pos < L) ? 1.f : 0.f;
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        const int n0 = (nf0 + f) * 16 + 4 * g4;       // this lane's 4 channels
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float a = acc16_val(acc[f][t])[e] * keep;
+          v[e] = fmaxf(a, a * d.slope);
+        }
+        bf16x4 q0, q1, q2;
+        bf3_split4(v, q0, q1, q2);
+        char* p = hs + (size_t)(col + off) * pitch + (size_t)(n0 >> 3) * 48 + (size_t)(n0 & 4) * 2;
+        *reinterpret_cast<bf16x4*>(p) = q0;
+        *reinterpret_cast<bf16x4*>(p + 16) = q1;
+        *reinterpret_cast<bf16x4*>(p + 32) = q2;
+      }
+    }
+    JATTS_STAMP(12);
+    lds_barrier();
+    JATTS_STAMP(4);
+
+    bias_acc(bs + C);
+    ws.bind((const T*)d.w2, KC32, NFR16, nf0, lane);     // (ra already holds w2's first step)
+    conv16<T, NF, NT, KC32>(acc, ws, 0, K, 1, hs, pitch, col0, lane, nullptr);
+    finish_acc();
+    JATTS_STAMP(5);
+
+    // ---- epilogue 2: acc (+ b2, already in) assembled as an f32 tile in LDS; the residual (and the MRF mean) are added in the row-contiguous store pass
+    __syncthreads();
+    if constexpr (SLIDE) {
+      // the next window's tail, h rows nout .. nout + K - 2: past the y tile (rows < nout, C * 4 of each row's C * 6 + 16 bytes)
+      for (int u = tid; u < (K - 1) * (C / 8); u += NTHR) {
+        const int r = u / (C / 8), cu = u % (C / 8);
+        Vec8IO<T>::sts(tl + (size_t)r * pitch_t + (size_t)cu * 48, Vec8IO<T>::lds(hs + (size_t)(nout + r) * pitch + (size_t)cu * 48));
+      }
+    }
+    char* ys = smem;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int col = col0 + t * 16 + (lane & 15);
+      if (col >= nvalid) continue;
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        const int n0 = (nf0 + f) * 16 + 4 * g4;
+        *reinterpret_cast<f32x4*>(ys + (size_t)col * pitch + (size_t)n0 * 4) = acc16_val(acc[f][t]);
+      }
+    }
+    __syncthreads();
+    JATTS_STAMP(6);
+    {
+      const int vrows = nvalid;
+      const int64_t g0 = (seq_row0 + t0) * (int64_t)C;
+      constexpr bool keep_small = C <= 64;
+      const float* xg = (const float*)d.x;
+      float* yg = (float*)d.y;
+      if constexpr (RREG) {
+        constexpr int UPR = C / 8;
+        const int n_out = vrows * UPR;
+        const bool has_add1 = d.add0 != nullptr && d.add1 != nullptr;
+        f32x8 a0[MAXI], a1[MAXI];
+        if (d.add0) {
+#pragma unroll
+          for (int j = 0; j < MAXI; ++j) {
+            const int v = tid + j * NTHR;
+            if (v < n_out) {
+              a0[j] = Vec8IO<float>::ldg((const float*)d.add0 + g0 + (int64_t)v * 8);
+              if (has_add1) a1[j] = Vec8IO<float>::ldg((const float*)d.add1 + g0 + (int64_t)v * 8);
+            }
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < MAXI; ++j) {
+          const int v = tid + j * NTHR;
+          if (v >= n_out) continue;
+          const int ro = v / UPR, cu = v - ro * UPR;
+          f32x8 o = Vec8IO<float>::lds(ys + (size_t)ro * pitch + (size_t)cu * 32);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) o[e] = o[e] + xk[j][e];          // residual
+          if (d.add0) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (o[e] + a0[j][e] + (has_add1 ? a1[j][e] : 0.f)) * d.out_scale;
+          }
+          float* dst = yg + g0 + (int64_t)v * 8;
+          *reinterpret_cast<f32x4*>(dst) = f32x4{o[0], o[1], o[2], o[3]};
+          *reinterpret_cast<f32x4*>(dst + 4) = f32x4{o[4], o[5], o[6], o[7]};
+        }
+      } else {
+        if (d.add0) unit_store_pass<float, C, keep_small ? 2 : 4, true, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
+        else unit_store_pass<float, C, keep_small ? 4 : 8, false, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
+      }
+    }
+    JATTS_STAMP(7);
+    if constexpr (!SLIDE) break;
+    // the next window: the run's next nout positions, carrying this one's tail -- or, past the sequence's end, the next sequence's first window
+    t0 += nout;
+    slide = true;
+    if (t0 >= L) {
+      f_seq += L;
+      if (f_seq >= f_end) break;
+      do { ++b; } while (d.rg.cu_rows[b + 1] == d.rg.cu_rows[b]);    // (an empty sequence has no positions; the run ends inside a later one)
+      t0 = 0;
+      slide = false;
+    } else if (f_seq + t0 >= f_end) {
+      break;
     }
   }
-  JATTS_STAMP(7);
   if (tracing) trace[(size_t)wg_lin * 16 + 9] = __builtin_amdgcn_s_memrealtime();
 #undef JATTS_STAMP
 }
 
+// The form of a launch: 1 = windowed, 2 = sliding.  variant 0 (the library's choice): sliding when its runs -- one per resident workgroup, CUs x OCC --
+// average two windows or more (the bench-size batches; a B = 1 utterance stays windowed: its ~1.6 windows per CU are better dealt out one by one).
+// slide_auto: the tile takes the sliding form by default at all.  A form whose tile does not fit the LDS is not taken.
+inline int resunit16_pick(const jatts_resunit_desc& d, int runs, int wgcols, bool slide_auto, bool slide_fits) {
+  const int64_t positions = ragged_is_1d(d.rg) ? (int64_t)d.rg.total_rows * d.rg.len_mul : (int64_t)d.rg.n_seq * d.rg.max_len * d.rg.len_mul;
+  const bool slide = d.variant == 2 || (d.variant == 0 && slide_auto && positions >= 2 * (int64_t)runs * wgcols);
+  return slide && slide_fits ? 2 : 1;
+}
+
+// `pick` non-null: report the form (resunit16_pick) instead of launching.
 template <typename T, int C, int WGCOLS, int WN, int WT, int OCC = 2, bool KSPLIT = false, bool RREG = false>
-int launch_resunit_emul16(const jatts_resunit_desc& d, hipStream_t s) {
+int launch_resunit_emul16(const jatts_resunit_desc& d, hipStream_t s, int* pick) {
   const int K = d.k_w, p2 = (K - 1) / 2, p1 = p2 * d.dil;
   const int tt_out = WGCOLS - 2 * p2;
   if (tt_out < 8) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: kernel too wide for tile");
   const size_t pitch = C * 6 + 16, pitch_x = KSPLIT ? (C / 2) * 6 + 16 : pitch;
   const size_t rows_x = WGCOLS + 2 * p1, rows_h = WGCOLS + K - 1;
   if (KSPLIT && 2 * p1 > 64) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit (emulated, channel halves): halo beyond 32 rows a side");
-  size_t lds = rows_x * pitch_x > rows_h * pitch ? rows_x * pitch_x : rows_h * pitch;
-  const unsigned bias_off = (unsigned)lds;
-  lds += 2 * C * sizeof(float);                                // b1 | b2
+  const size_t region = rows_x * pitch_x > rows_h * pitch ? rows_x * pitch_x : rows_h * pitch;
+  const size_t tail = (size_t)(K - 1) * C * 6;                  // SLIDE: the parked h tail
+  const size_t lds = region + 2 * C * sizeof(float);            // + b1 | b2
   if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: tile exceeds 160 KiB LDS");
-  const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
-  dim3 grid((unsigned)((maxL + tt_out - 1) / tt_out), (unsigned)d.rg.n_seq);
-  if (const int64_t n1 = ragged_tiles_1d(d.rg, tt_out)) grid = dim3((unsigned)n1);
-  auto kern = resunit_emul16_kernel<T, C, WGCOLS, WN, WT, OCC, KSPLIT, RREG>;
-  JATTS_RAISE_LDS_LIMIT(kern);
-  hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, jatts_g_trace, jatts_g_trace_cap, bias_off);
+  int dev = 0, cus = 0;     // asked per launch: the device can differ from call to call
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e != hipSuccess) return jatts_set_error(e, __FILE__, __LINE__);
+  const int runs = cus * OCC;
+  // (the residual-register tiles, C <= 64, stay windowed unless forced: their sliding instantiation spills at seven products -- the window loop keeps
+  //  more state live than the register budget of their tiles leaves)
+  const int form = resunit16_pick(d, runs, WGCOLS, !RREG, lds + tail <= 160 * 1024);
+  if (pick) {
+    *pick = form;
+    return JATTS_OK;
+  }
+  if (form == 2) {
+    auto kern = resunit_emul16_kernel<T, C, WGCOLS, WN, WT, OCC, KSPLIT, RREG, true>;
+    JATTS_RAISE_LDS_LIMIT(kern);
+    hipLaunchKernelGGL(kern, dim3((unsigned)runs), dim3(WN * WT * 64), lds + tail, s, d, jatts_g_trace, jatts_g_trace_cap, (unsigned)(region + tail));
+  } else {
+    const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
+    dim3 grid((unsigned)((maxL + tt_out - 1) / tt_out), (unsigned)d.rg.n_seq);
+    if (const int64_t n1 = ragged_tiles_1d(d.rg, tt_out)) grid = dim3((unsigned)n1);
+    auto kern = resunit_emul16_kernel<T, C, WGCOLS, WN, WT, OCC, KSPLIT, RREG>;
+    JATTS_RAISE_LDS_LIMIT(kern);
+    hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, jatts_g_trace, jatts_g_trace_cap, (unsigned)region);
+  }
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }

@@ -645,12 +645,9 @@ def _check_unit_weights(who, dtype, channels, k_w, *ws):
                              f"pack_conv_weight_bf16x3 with c_mult=32), got {w.numel()} x {w.dtype}")
 
 
-def hifigan_resunit(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, dtype, add=None, out_scale=1.0, ws=None, w_layout=0):
-    """jatts_hifigan_resunit.  w_layout (F32E / F32E6): 0 = weights from pack_conv_weight_bf16x3(w, 32) (32 x 32 x 16 kernels), 1 = from
-    pack_unit_weight_bf16x3_k32 (16 x 16 x 32 kernels)."""
-    lib = _abi.load()
+def _resunit_desc(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, dtype, add, out_scale, ws, w_layout, variant):
     d = _abi.ResUnitDesc()
-    d.w_layout = w_layout
+    d.w_layout, d.variant = w_layout, variant
     d.rg = rb.struct(len_mul)
     d.dtype, d.channels, d.k_w, d.dil, d.slope = dtype, channels, k_w, dil, slope
     rows = rb.total * len_mul
@@ -670,9 +667,26 @@ def hifigan_resunit(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope
         d.add0 = add[0].data_ptr()
         d.add1 = add[1].data_ptr() if len(add) > 1 else None
     d.out_scale = out_scale
-    with _Timed("resunit", (channels, k_w, dil, rows, len(add) if add else 0)):
+    return d
+
+
+def hifigan_resunit(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, dtype, add=None, out_scale=1.0, ws=None, w_layout=0, variant=0):
+    """jatts_hifigan_resunit.  w_layout (F32E / F32E6): 0 = weights from pack_conv_weight_bf16x3(w, 32) (32 x 32 x 16 kernels), 1 = from
+    pack_unit_weight_bf16x3_k32 (16 x 16 x 32 kernels).  variant (jatts_resunit_desc.variant): 0 = the library's choice, 1 = windowed, 2 = sliding."""
+    lib = _abi.load()
+    d = _resunit_desc(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, dtype, add, out_scale, ws, w_layout, variant)
+    with _Timed("resunit", (channels, k_w, dil, rb.total * len_mul, len(add) if add else 0)):
         _abi.check(lib.jatts_hifigan_resunit(C.byref(d), _stream()), "jatts_hifigan_resunit")
     return y
+
+
+def resunit_variant(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, dtype, add=None, out_scale=1.0, ws=None, w_layout=0, variant=0):
+    """jatts_resunit_variant: the form hifigan_resunit with the same arguments would launch (1 = windowed, 2 = sliding); launches nothing."""
+    lib = _abi.load()
+    d = _resunit_desc(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, dtype, add, out_scale, ws, w_layout, variant)
+    rc = lib.jatts_resunit_variant(C.byref(d))
+    _abi.check(min(rc, 0), "jatts_resunit_variant")
+    return rc
 
 
 def hifigan_resblock(rb, len_mul, x, y, units, channels, k_w, slope, dtype, add=None, out_scale=1.0, ws=None):

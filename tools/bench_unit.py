@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the fused HiFi-GAN dilation-unit kernel at bench-sized shapes.
-    python tools/bench_unit.py [--C 128 --k 11 --dil 1 --iters 10] [--all]
-Prints avg ms, TFLOP/s and algorithmic GB/s per shape (HIP events on the launch stream)."""
+    python tools/bench_unit.py [--C 128 --k 11 --dil 1 --iters 10] [--all] [--variant 0|1|2 | --variants]
+Prints avg ms, TFLOP/s and algorithmic GB/s per shape (HIP events on the launch stream).  --variants (emulated units): the windowed and the sliding
+form of every shape side by side (jatts_resunit_desc.variant 1 / 2)."""
 import argparse
 import os
 import sys
@@ -15,7 +16,7 @@ from jatts_amd import hip  # noqa: E402
 LAYOUT = [1]      # emulated units: 1 = the v_mfma_f32_16x16x32_bf16 kernels (the product form), 0 = the 32 x 32 x 16 ones (--layout 0)
 
 
-def run(C, k, d, rate, iters, B=64, T=768, dtype=hip.F16):
+def run(C, k, d, rate, iters, B=64, T=768, dtype=hip.F16, variant=0):
     dev = torch.device("cuda:0")
     rb = hip.RaggedBatch([T] * B, dev)
     rows = B * T * rate
@@ -32,6 +33,7 @@ def run(C, k, d, rate, iters, B=64, T=768, dtype=hip.F16):
         if LAYOUT[0]:
             w1, w2 = hip.pack_unit_weight_bf16x3_k32(wa), hip.pack_unit_weight_bf16x3_k32(wb)
             kw["w_layout"] = 1
+            kw["variant"] = variant
         else:
             w1, w2 = hip.pack_conv_weight_bf16x3(wa, 32), hip.pack_conv_weight_bf16x3(wb, 32)
     else:
@@ -50,7 +52,8 @@ def run(C, k, d, rate, iters, B=64, T=768, dtype=hip.F16):
     ms = a.elapsed_time(b) / iters
     flops = 4.0 * C * C * k * rows
     byts = 2.0 * rows * C * x.element_size()
-    print(f"C={C:4d} k={k:2d} d={d} rows={rows:9d}  {ms:7.3f} ms  {flops / ms / 1e9:7.1f} TFLOP/s  {byts / ms / 1e6:7.1f} GB/s")
+    form = f"  form {hip.resunit_variant(rb, rate, x, y, w1, b1, w2, b2, C, k, d, 0.1, dtype, **kw)}" if "variant" in kw else ""
+    print(f"C={C:4d} k={k:2d} d={d} rows={rows:9d}  {ms:7.3f} ms  {flops / ms / 1e9:7.1f} TFLOP/s  {byts / ms / 1e6:7.1f} GB/s{form}")
     return ms
 
 
@@ -114,6 +117,8 @@ def main():
     ap.add_argument("--dtype", default="f16", choices=["f16", "f32", "split", "emul", "emul6"])
     ap.add_argument("--resblock", action="store_true", help="fused ResBlock launches vs per-unit launches (f16)")
     ap.add_argument("--layout", type=int, default=1, choices=[0, 1], help="emulated units: 1 = v_mfma_f32_16x16x32_bf16 kernels (product), 0 = 32x32x16")
+    ap.add_argument("--variant", type=int, default=0, choices=[0, 1, 2], help="emulated units, layout 1: 0 = the library's form, 1 = windowed, 2 = sliding")
+    ap.add_argument("--variants", action="store_true", help="emulated units, layout 1: time the windowed and the sliding form of every shape")
     a = ap.parse_args()
     rates = {256: 8, 128: 64, 64: 128, 32: 256}  # HiFi-GAN v1 22.05 kHz stage rates
     dt = {"f16": hip.F16, "f32": hip.F32, "split": hip.F32S, "emul": hip.F32E, "emul6": hip.F32E6}[a.dtype]
@@ -125,15 +130,18 @@ def main():
                     continue
                 run_block(C, k, rates[C], a.iters, dt=dt)
         return
+    variants = (1, 2) if a.variants else (a.variant,)
+    shapes = [(C, k, d) for C in (256, 128, 64, 32) for k in (3, 7, 11) for d in (1, 3, 5)] if a.all else [(a.C, a.k, a.dil)]
+    tot = {v: 0.0 for v in variants}
+    for C, k, d in shapes:
+        ms = {v: run(C, k, d, rates[C], a.iters, B=a.batch, dtype=dt, variant=v) for v in variants}
+        for v in variants:
+            tot[v] += ms[v]
+        if len(variants) == 2:
+            print(f"    sliding / windowed = {ms[2] / ms[1]:.4f}")
     if a.all:
-        tot = 0.0
-        for C in (256, 128, 64, 32):
-            for k in (3, 7, 11):
-                for d in (1, 3, 5):
-                    tot += run(C, k, d, rates[C], a.iters, dtype=dt)
-        print(f"sum over the 36 units of one generator pass: {tot:.2f} ms")
-    else:
-        run(a.C, a.k, a.dil, rates[a.C], a.iters, B=a.batch, dtype=dt)
+        for v in variants:
+            print(f"sum over the 36 units of one generator pass{'' if len(variants) == 1 else f' (variant {v})'}: {tot[v]:.2f} ms")
 
 
 if __name__ == "__main__":
