@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define JATTS_ABI_VERSION 5   /* 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
+#define JATTS_ABI_VERSION 6   /* 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
                                 * so every descriptor that embeds it (jatts_conv_desc, jatts_resunit_desc, jatts_resblock_desc, jatts_relattn_desc) shifted by 8 bytes; JATTS_F32E; 2 (round 4): jatts_conv_desc + w_inv / act_a / act_b, jatts_resunit_desc + ws1 / ws2, jatts_resblock_desc + ws1 / ws2;
                                 * bumped whenever a descriptor's layout or an entry point's signature changes: a stale library is refused at load */
 
@@ -284,6 +284,20 @@ int jatts_pack_conv_weight(const float* w, int32_t n_out, int32_t c_in, int32_t 
  * w * 2^s[n]; inv: pad32(n) floats, 2^-s[n] (1 for all-zero and padding rows).  Two launches (row maxima, pack); deterministic. */
 int jatts_pack_conv_weight_split(const float* w, int32_t n_out, int32_t c_in, int32_t k_w, int32_t c_mult, int32_t mode, void* out, float* inv,
                                  void* stream);
+/* The same for the JATTS_F32E operand in the fragment order of the 16 x 16 x 32 kernels (jatts_conv_desc.w_layout = 1), for weights that change every step
+ * (torch.nn.Conv1d's weight under jatts/trainers/fastspeech2.py:86-96: backward, clip, optimizer.step): ONE launch, no scales.
+ * out: 3 * k_w * pad32(n) * pad(c, c_mult) bf16 = [tap][c/32][n/16][lane = 16 ((c % 32) / 8) + n % 16][b0 x8 | b1 x8 | b2 x8] over c % 8, pad entries zero;
+ * b0 = bf16(w), b1 = bf16(w - b0), b2 = bf16(w - b0 - b1), round to nearest even.  c_mult: a multiple of 32 (64 for jatts_conv1d).
+ * dgrad = 1 packs the data-gradient operand W'[c][n][k'] = W[n][c][k_w-1-k'] (padded sizes follow the swapped roles). */
+int jatts_pack_conv_weight_bf16x3(const float* w, int32_t n_out, int32_t c_in, int32_t k_w, int32_t c_mult, int32_t dgrad, void* out, void* stream);
+/* jatts_conv1d_wgrad on the f32-equivalent emulated arithmetic (torch.nn.Conv1d's weight.grad / bias.grad under jatts/trainers/fastspeech2.py:86,
+ * gen_loss.backward): dtype JATTS_F32E -- both operands split into three bf16 terms while they are staged, seven partial products on
+ * v_mfma_f32_16x16x32_bf16, leading and small products in separate accumulators joined by one add per workgroup (a one-term sum is within
+ * 2.01 x 2^-24 of dy x); JATTS_F32E6 is refused.  k_w 1 / 3 / 5 with (k_w - 1) dil <= 32; any other geometry returns through the exact-f32 entry.
+ * Same arguments and workspace contract as jatts_conv1d_wgrad (workspace required, dw and db OVERWRITTEN, fixed-order split-K: two runs are
+ * bit-identical); db is summed in exact f32 from the staged dy tiles. */
+int jatts_conv1d_wgrad_emul(const jatts_ragged* rg, const float* x, int32_t ldx, const float* dy, int32_t ldy, int32_t c_in, int32_t n_out, int32_t k_w,
+                            int32_t dil, int32_t pad, int32_t dtype, float* dw, float* db, float* workspace, void* stream);
 /* out[c] += sum over rows of x[row][c] (bias gradient; caller zeroes out). */
 int jatts_col_sum(const float* x, int32_t ld, int64_t rows, int32_t dim, float* out, void* stream);
 

@@ -4,6 +4,7 @@
 // variance_predictor_loss}.py, torch.nn.Conv1d's autograd.
 #include "common.h"
 #include "det_reduce.h"
+#include "resunit_emul16_impl.h"   // acc2x4 / mma16p: the seven-product rule of the emulated convs, shared with the emulated weight gradient below
 
 namespace {
 
@@ -337,6 +338,233 @@ __global__ __launch_bounds__(256) void pack_conv_weight_split_kernel(const float
   }
 }
 
+// The JATTS_F32E operand of a TRAINING weight (round 7): [tap][c / 32][n / 16][lane = 16 ((c % 32) / 8) + n % 16][b0 x8 | b1 x8 | b2 x8] over c % 8
+// (jatts_conv_desc.w_layout = 1, conv1d_emul16.h), n zero-padded to 32 and c to c_mult, the three terms by round-to-nearest-even (bf3_split8: the roundings of
+// hip.bf16x3_terms in the same order) -- in ONE launch, mode 1 packing the data-gradient operand W'[c][n][K - 1 - tap] directly.  One thread = one lane's
+// 8 channels of one fragment: eight strided f32 reads, three 16-byte stores.
+__global__ __launch_bounds__(256) void pack_conv_weight_bf16x3_kernel(const float* __restrict__ w, int n_out, int c_in, int K, int n_pad, int c_pad, int mode,
+                                                                      bf16* __restrict__ out) {
+  const int64_t total = (int64_t)K * n_pad * (c_pad / 8);
+  const int KC32 = c_pad / 32, NFR16 = n_pad / 16;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int lane = (int)(i & 63);
+    int64_t r = i >> 6;
+    const int nf = (int)(r % NFR16);
+    r /= NFR16;
+    const int c32 = (int)(r % KC32), tap = (int)(r / KC32);
+    const int n = nf * 16 + (lane & 15), c0 = c32 * 32 + (lane >> 4) * 8;
+    f32x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = c0 + e;
+      float t = 0.f;
+      if (mode == 0) {
+        if (n < n_out && c < c_in) t = w[((int64_t)n * c_in + c) * K + tap];
+      } else {        // packed "n" runs over the original input channels, packed "c" over the original output channels
+        if (n < c_in && c < n_out) t = w[((int64_t)c * c_in + n) * K + (K - 1 - tap)];
+      }
+      v[e] = t;
+    }
+    bf3px8<7> o;
+    bf3_split8<7>(v, o);
+    bf16x8* dst = reinterpret_cast<bf16x8*>(out + i * 24);
+    dst[0] = o.b0;
+    dst[1] = o.b1;
+    dst[2] = o.b2;
+  }
+}
+
+// The weight gradient on the f32-EQUIVALENT emulated arithmetic (JATTS_F32E, round 7): dW[n][c][tap] = sum_t dy[t][n] x[t + tap dil - pad][c] as
+// v_mfma_f32_16x16x32_bf16 with A = dy^T (rows n), B = x (columns c) and the contraction over TIME.  Both operands are activations: every f32 value is split
+// into its three bf16 terms while it is staged (bf3_split2, no scales), seven of the nine partial products are issued, the leading product and the six small
+// ones go to separate accumulators joined by ONE add at the end of the workgroup's K range (acc2x4 / mma16p: the rule of conv1d_emul16.h, same per-product
+// bound).
+//
+// The transposition.  HBM rows are channel-contiguous, the MFMA wants 8 consecutive TIME steps per lane for both operands.  The split planes are staged
+// time-fastest -- [plane][channel][t] bf16, 64 (dy) / 64 + 32 (x, with its halo) steps per row -- so a fragment is one ds_read_b128 per plane:
+//  * a staging thread owns 4 consecutive time steps x 4 channels (four 16-byte global loads); bf3_split2 splits two time steps of one channel at a time, its
+//    result is already the stored pair, and a channel's four steps of a plane go out as one ds_write_b64;
+//  * row pitch = 32 x odd bytes (160 / 224): the 16-lane groups of a ds_read_b128 ({0-3, 12-15, 20-27}, ...) read rows r and K-groups g at 16-byte segments
+//    2 m r + g (mod 16) -- even for the lanes of one K-group, odd for those of the next: conflict-free; the 16 lanes of a ds_write_b64 group are 16 consecutive
+//    4-step row groups of one channel: banks 2 g, conflict-free;
+//  * the x tile is staged ONCE per chunk and serves every tap by an offset of tap dil steps in t.  An offset that is a multiple of 8 keeps the 16-byte read;
+//    any other one reads five 4-byte-aligned dwords and funnel-shifts them (v_alignbit_b32) -- a misaligned ds_read_b128 would be replayed at 64 cycles.
+// A workgroup (4 waves, each 32 n x 32 c = 2 x 2 fragments, for ALL taps) owns a 64 x 64 tile over a slice of the sequences; the next chunk's global loads
+// are in flight under this chunk's MFMAs (registers), 66 KiB of LDS = two workgroups per CU.  Split-K partials and the bias partials (f32 column sums of the
+// staged dy, as the exact-f32 kernel) go to the caller's workspace in conv_wgrad_mfma_kernel's layout; wgrad_reduce_kernel sums them in a fixed order.
+constexpr int WE_TT = 64, WE_HALO = 32;
+constexpr int WE_PD = WE_TT * 2 + 32, WE_PX = (WE_TT + WE_HALO) * 2 + 32;        // 160, 224 bytes: 32 x odd
+constexpr int WE_DPLANE = 64 * WE_PD, WE_XPLANE = 64 * WE_PX;
+constexpr int WE_LDS = 3 * (WE_DPLANE + WE_XPLANE);
+static_assert(WE_PD % 64 == 32 && WE_PX % 64 == 32, "row pitch must be 32 x odd bytes");
+
+// four time steps x four channels -> three planes, one ds_write_b64 per channel and plane
+__device__ __forceinline__ void we_commit4(char* base, int plane_bytes, int pitch, int ch0, int t_local, const f32x4 (&v)[4]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    bf16x2 a0, a1, a2, b0, b1, b2;
+    bf3_split2(v[0][e], v[1][e], a0, a1, a2);
+    bf3_split2(v[2][e], v[3][e], b0, b1, b2);
+    char* p = base + (size_t)(ch0 + e) * pitch + (size_t)t_local * 2;
+    *reinterpret_cast<uint2*>(p) = make_uint2(__builtin_bit_cast(unsigned, a0), __builtin_bit_cast(unsigned, b0));
+    *reinterpret_cast<uint2*>(p + plane_bytes) = make_uint2(__builtin_bit_cast(unsigned, a1), __builtin_bit_cast(unsigned, b1));
+    *reinterpret_cast<uint2*>(p + 2 * plane_bytes) = make_uint2(__builtin_bit_cast(unsigned, a2), __builtin_bit_cast(unsigned, b2));
+  }
+}
+// 8 consecutive time steps of one plane starting at an ODD-aligned step: five dwords from the 4-byte-aligned address below it, shifted by `sh` (0 / 16) bits
+__device__ __forceinline__ bf16x8 we_read_shifted(const char* p4, unsigned sh) {
+  const unsigned* q = reinterpret_cast<const unsigned*>(p4);
+  const unsigned d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 o = {__builtin_amdgcn_alignbit(d1, d0, sh), __builtin_amdgcn_alignbit(d2, d1, sh), __builtin_amdgcn_alignbit(d3, d2, sh),
+                   __builtin_amdgcn_alignbit(d4, d3, sh)};
+  return __builtin_bit_cast(bf16x8, o);
+}
+
+template <int KW>
+__global__ __launch_bounds__(256, KW == 5 ? 1 : 2) void conv_wgrad_emul_kernel(jatts_ragged rg, const float* __restrict__ x, int ldx,
+                                                                                const float* __restrict__ dy, int ldy, int c_in, int n_out, int dil, int pad,
+                                                                                int seq_groups, float* __restrict__ ws, float* __restrict__ bws) {
+  extern __shared__ __attribute__((aligned(16))) char wsm[];
+  char* const dyb = wsm;
+  char* const xb = wsm + 3 * WE_DPLANE;
+  const int halo = (KW - 1) * dil;
+  const int n0 = blockIdx.x * 64, c0 = blockIdx.y * 64, grp = blockIdx.z;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wn = wave >> 1, wc = wave & 1;
+  const bool vec_dy = (ldy & 3) == 0 && n0 + 64 <= n_out && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
+  const bool vec_x = (ldx & 3) == 0 && c0 + 64 <= c_in && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  acc2x4 acc[KW][2][2];
+#pragma unroll
+  for (int k = 0; k < KW; ++k)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc16_set(acc[k][a][b], e, 0.f);
+  // staging units: 4 time steps x 4 channels; the 16 lanes of a store group are 16 consecutive row groups of one channel quad.
+  // dy: 16 row groups x 16 quads = one unit per thread; x: up to 24 row groups -- a second unit (row groups 16 ..) on the threads whose lane & 15 < 8
+  const int ug = threadIdx.x & 15, uq = threadIdx.x >> 4;
+  const int nxg = (WE_TT + halo + 3) >> 2;                 // x row groups in use
+  const bool x2 = ug < 8 && 16 + ug < nxg;
+  f32x4 rdy[4], rx[2][4];
+  const bool do_b = bws != nullptr && blockIdx.y == 0;
+  f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
+  auto load4 = [&](const float* base, int ld, int64_t row0, int L, int p0, int col, bool vec, int lim, f32x4 (&dst)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int p = p0 + i;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (p >= 0 && p < L) {
+        const float* src = base + (row0 + p) * ld + col;
+        if (vec) v = *reinterpret_cast<const f32x4*>(src);
+        else
+#pragma unroll
+          for (int e = 0; e < 4; ++e) if (col + e < lim) v[e] = src[e];
+      }
+      dst[i] = v;
+    }
+  };
+  auto issue = [&](int s, int t0) {
+    const int64_t row0 = (int64_t)rg.cu_rows[s] * rg.len_mul;
+    const int L = (rg.cu_rows[s + 1] - rg.cu_rows[s]) * rg.len_mul;
+    load4(dy, ldy, row0, L, t0 + 4 * ug, n0 + 4 * uq, vec_dy, n_out, rdy);
+    load4(x, ldx, row0, L, t0 - pad + 4 * ug, c0 + 4 * uq, vec_x, c_in, rx[0]);
+    if (x2) load4(x, ldx, row0, L, t0 - pad + 4 * (16 + ug), c0 + 4 * uq, vec_x, c_in, rx[1]);
+  };
+  auto commit = [&]() {
+    we_commit4(dyb, WE_DPLANE, WE_PD, 4 * uq, 4 * ug, rdy);
+    if (do_b) bsum += (rdy[0] + rdy[1]) + (rdy[2] + rdy[3]);
+    we_commit4(xb, WE_XPLANE, WE_PX, 4 * uq, 4 * ug, rx[0]);
+    if (x2) we_commit4(xb, WE_XPLANE, WE_PX, 4 * uq, 4 * (16 + ug), rx[1]);
+  };
+  // fragment addresses: lane supplies row / column (lane & 15) and the time steps 8 (lane >> 4) .. + 7 of a 32-step K-step
+  const char* ap = dyb + (size_t)(wn * 32 + (lane & 15)) * WE_PD + (size_t)(lane >> 4) * 16;
+  const char* bp = xb + (size_t)(wc * 32 + (lane & 15)) * WE_PX + (size_t)(lane >> 4) * 16;
+  int cs = grp, ct0 = 0;
+  if (cs < rg.n_seq) issue(cs, ct0);
+  while (cs < rg.n_seq) {
+    commit();
+    __syncthreads();
+    const int Lc = (rg.cu_rows[cs + 1] - rg.cu_rows[cs]) * rg.len_mul;
+    int ns = cs, nt0 = ct0 + WE_TT;                  // next chunk: its loads fly under this chunk's MFMAs
+    if (nt0 >= Lc) { ns = cs + seq_groups; nt0 = 0; }
+    if (ns < rg.n_seq) issue(ns, nt0);
+#pragma unroll
+    for (int ks = 0; ks < WE_TT / 32; ++ks) {
+      bf3px8<7> a[2];
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+        const char* p = ap + (size_t)f * 16 * WE_PD + ks * 64;
+        a[f].b0 = *reinterpret_cast<const bf16x8*>(p);
+        a[f].b1 = *reinterpret_cast<const bf16x8*>(p + WE_DPLANE);
+        a[f].b2 = *reinterpret_cast<const bf16x8*>(p + 2 * WE_DPLANE);
+      }
+#pragma unroll
+      for (int k = 0; k < KW; ++k) {
+        const int off = k * dil;
+        bf3px8<7> b[2];
+        if ((off & 7) == 0) {     // (wave-uniform)
+#pragma unroll
+          for (int f = 0; f < 2; ++f) {
+            const char* p = bp + (size_t)f * 16 * WE_PX + ks * 64 + off * 2;
+            b[f].b0 = *reinterpret_cast<const bf16x8*>(p);
+            b[f].b1 = *reinterpret_cast<const bf16x8*>(p + WE_XPLANE);
+            b[f].b2 = *reinterpret_cast<const bf16x8*>(p + 2 * WE_XPLANE);
+          }
+        } else {
+          const unsigned sh = (unsigned)(off & 1) * 16u;
+#pragma unroll
+          for (int f = 0; f < 2; ++f) {
+            const char* p = bp + (size_t)f * 16 * WE_PX + ks * 64 + (off & ~1) * 2;
+            b[f].b0 = we_read_shifted(p, sh);
+            b[f].b1 = we_read_shifted(p + WE_XPLANE, sh);
+            b[f].b2 = we_read_shifted(p + 2 * WE_XPLANE, sh);
+          }
+        }
+#define JATTS_WE_P(P_)                                     \
+  mma16p<P_>(a[0], b[0], acc[k][0][0]); mma16p<P_>(a[0], b[1], acc[k][0][1]); \
+  mma16p<P_>(a[1], b[0], acc[k][1][0]); mma16p<P_>(a[1], b[1], acc[k][1][1]);
+        JATTS_WE_P(0) JATTS_WE_P(1) JATTS_WE_P(2) JATTS_WE_P(3) JATTS_WE_P(4) JATTS_WE_P(5) JATTS_WE_P(6)
+#undef JATTS_WE_P
+      }
+    }
+    __syncthreads();
+    cs = ns; ct0 = nt0;
+  }
+  if (do_b) {   // (uniform per workgroup; the loop ended on a barrier, LDS is free): fold the 16 row-group threads of every channel quad, fixed order
+    float* sf = reinterpret_cast<float*>(wsm);
+    *reinterpret_cast<f32x4*>(&sf[threadIdx.x * 4]) = bsum;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+      const int q = threadIdx.x >> 2, e = threadIdx.x & 3;
+      float s = 0.f;
+#pragma unroll
+      for (int g = 0; g < 16; ++g) s += sf[(q * 16 + g) * 4 + e];
+      bws[(int64_t)grp * gridDim.x * 64 + n0 + threadIdx.x] = s;
+    }
+  }
+  // C / D map of the 16 x 16 fragment: column (lane & 15) = c, rows 4 (lane >> 4) + reg = n.  ws[grp][tap][n][c] as conv_wgrad_mfma_kernel
+  const int n64 = gridDim.x * 64, c64 = gridDim.y * 64;
+  float* o = ws + (int64_t)grp * KW * n64 * c64;
+#pragma unroll
+  for (int k = 0; k < KW; ++k)
+#pragma unroll
+    for (int fa = 0; fa < 2; ++fa)
+#pragma unroll
+      for (int fb = 0; fb < 2; ++fb) {
+        acc16_finish(acc[k][fa][fb]);      // the ONE add that joins the leading product's accumulator and the small products'
+        const f32x4 v = acc16_val(acc[k][fa][fb]);
+        const int c = c0 + wc * 32 + fb * 16 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int n = n0 + wn * 32 + fa * 16 + 4 * (lane >> 4) + r;
+          o[((int64_t)k * n64 + n) * c64 + c] = v[r];
+        }
+      }
+}
+
 // out[c] += sum over rows of x[row][c]
 __global__ __launch_bounds__(256) void col_sum_kernel(const float* x, int ld, int64_t rows, int dim, float* out, int overwrite,
                                                       float* __restrict__ slabs, unsigned* __restrict__ tickets) {
@@ -405,6 +633,25 @@ extern "C" int jatts_masked_loss(const jatts_ragged* rg, const float* a, int32_t
   return JATTS_OK;
 }
 
+// Sequence groups (split-K factor) of the MFMA weight-gradient kernels: the launch ends when the fullest CU has walked its workgroups, each over
+// ceil(n_seq / g) sequences -- minimise ceil(tiles g / 256) ceil(n_seq / g) (the old "at least 1 536 workgroups" rule gave 1 584 for 1536 x 384: 7 on some CUs, 6
+// on others, each 3 sequences long = 21 units against 18 for g = 16: 840 -> 782 us), preferring four resident
+// workgroups per CU, with a small tax per group for the reduction pass.  Deterministic: a function of the shapes only.
+static int wgrad_seq_groups(int tiles_m, int n_seq) {
+  int g = 1;
+  double best = 1e300;
+  for (int c = 1; c <= n_seq; ++c) {
+    const int64_t wgs = (int64_t)tiles_m * c;
+    double cost = (double)((wgs + 255) / 256) * (double)((n_seq + c - 1) / c);
+    const int64_t per_cu = (wgs + 255) / 256;
+    if (wgs < 512) cost *= 512.0 / (double)wgs;
+    if (per_cu < 4) cost *= 1.0 + 0.06 * (double)(4 - per_cu);   // four resident workgroups per CU hide the staging (2048 x 512 k1: g = 2 638 us, g = 4 544 us)
+    cost *= 1.0 + 0.002 * c;
+    if (cost < best) { best = cost; g = c; }
+  }
+  return g;
+}
+
 extern "C" int jatts_conv1d_wgrad(const jatts_ragged* rg, const float* x, int32_t ldx, const float* dy, int32_t ldy, int32_t c_in,
                                   int32_t n_out, int32_t k_w, int32_t dil, int32_t pad, float* dw, float* db, float* workspace, void* stream) {
   if (!rg || !x || !dy || !dw) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad: null pointer");
@@ -416,23 +663,7 @@ extern "C" int jatts_conv1d_wgrad(const jatts_ragged* rg, const float* x, int32_
   if (groups < 1) groups = 1;
   if ((k_w == 1 || k_w == 3 || k_w == 5) && (k_w - 1) * dil <= 32) {
     const int tiles_m = ((n_out + 63) / 64) * ((c_in + 63) / 64);
-    // Sequence groups (split-K factor): the launch ends when the fullest CU has walked its workgroups, each over ceil(n_seq / g) sequences
-    // -- minimise ceil(tiles g / 256) ceil(n_seq / g) (the old "at least 1 536 workgroups" rule gave 1 584 for 1536 x 384: 7 on some CUs, 6
-    // on others, each 3 sequences long = 21 units against 18 for g = 16: 840 -> 782 us), preferring four resident
-    // workgroups per CU, with a small tax per group for the reduction pass.  Deterministic: a function of the shapes only.
-    int g = 1;
-    {
-      double best = 1e300;
-      for (int c = 1; c <= rg->n_seq; ++c) {
-        const int64_t wgs = (int64_t)tiles_m * c;
-        double cost = (double)((wgs + 255) / 256) * (double)((rg->n_seq + c - 1) / c);
-        const int64_t per_cu = (wgs + 255) / 256;
-        if (wgs < 512) cost *= 512.0 / (double)wgs;
-        if (per_cu < 4) cost *= 1.0 + 0.06 * (double)(4 - per_cu);   // four resident workgroups per CU hide the staging (2048 x 512 k1: g = 2 638 us, g = 4 544 us)
-        cost *= 1.0 + 0.002 * c;
-        if (cost < best) { best = cost; g = c; }
-      }
-    }
+    const int g = wgrad_seq_groups(tiles_m, rg->n_seq);
     const dim3 grid((unsigned)((n_out + 63) / 64), (unsigned)((c_in + 63) / 64), (unsigned)g);
     const size_t lds = 2 * (size_t)(64 + (k_w - 1) * dil) * 68 * sizeof(float);   // two buffers of (dy tile | x tile + halo)
     // bias partials live behind the weight partials: workspace[g k n64 c64 ..][g][n64]
@@ -461,6 +692,37 @@ extern "C" int jatts_conv1d_wgrad(const jatts_ragged* rg, const float* x, int32_
   }
   hipLaunchKernelGGL(conv_wgrad_kernel, dim3((unsigned)((n_out + 63) / 64), (unsigned)((c_in + 63) / 64), (unsigned)(k_w * groups)), dim3(256), 0, S_,
                      *rg, x, ldx, dy, ldy, c_in, n_out, k_w, dil, pad, groups, dw, workspace ? 1 : 0, jatts_g_ws.slabs, jatts_g_ws.tickets);
+  JATTS_CHECK_LAUNCH();
+  return JATTS_OK;
+}
+
+extern "C" int jatts_conv1d_wgrad_emul(const jatts_ragged* rg, const float* x, int32_t ldx, const float* dy, int32_t ldy, int32_t c_in, int32_t n_out,
+                                       int32_t k_w, int32_t dil, int32_t pad, int32_t dtype, float* dw, float* db, float* workspace, void* stream) {
+  if (dtype == JATTS_F32E6) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d_wgrad_emul: the six-product arithmetic (JATTS_F32E6) has no weight gradient");
+  if (dtype != JATTS_F32E) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: dtype must be JATTS_F32E");
+  if (!rg || !x || !dy || !dw) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: null pointer");
+  if (c_in < 1 || n_out < 1 || k_w < 1 || dil < 1) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: bad geometry");
+  // outside the emulated kernel's taps / halo: the exact-f32 entry (the more accurate of the two)
+  if (!(k_w == 1 || k_w == 3 || k_w == 5) || (k_w - 1) * dil > WE_HALO) return jatts_conv1d_wgrad(rg, x, ldx, dy, ldy, c_in, n_out, k_w, dil, pad, dw, db, workspace, stream);
+  if (rg->n_seq <= 0 || rg->max_len <= 0) return JATTS_OK;
+  if (!workspace) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: needs the split-K workspace of jatts_conv1d_wgrad (see include/jatts_hip.h)");
+  const int tiles_m = ((n_out + 63) / 64) * ((c_in + 63) / 64);
+  const int g = wgrad_seq_groups(tiles_m, rg->n_seq);
+  const dim3 grid((unsigned)((n_out + 63) / 64), (unsigned)((c_in + 63) / 64), (unsigned)g);
+  float* bws = db ? workspace + (int64_t)g * k_w * grid.x * 64 * grid.y * 64 : nullptr;
+  if (k_w == 1) {
+    JATTS_RAISE_LDS_LIMIT(conv_wgrad_emul_kernel<1>);
+    hipLaunchKernelGGL(conv_wgrad_emul_kernel<1>, grid, dim3(256), WE_LDS, S_, *rg, x, ldx, dy, ldy, c_in, n_out, dil, pad, g, workspace, bws);
+  } else if (k_w == 3) {
+    JATTS_RAISE_LDS_LIMIT(conv_wgrad_emul_kernel<3>);
+    hipLaunchKernelGGL(conv_wgrad_emul_kernel<3>, grid, dim3(256), WE_LDS, S_, *rg, x, ldx, dy, ldy, c_in, n_out, dil, pad, g, workspace, bws);
+  } else {
+    JATTS_RAISE_LDS_LIMIT(conv_wgrad_emul_kernel<5>);
+    hipLaunchKernelGGL(conv_wgrad_emul_kernel<5>, grid, dim3(256), WE_LDS, S_, *rg, x, ldx, dy, ldy, c_in, n_out, dil, pad, g, workspace, bws);
+  }
+  const int64_t total = (int64_t)n_out * c_in * k_w;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048)), dim3(256), 0, S_, workspace, g, k_w,
+                     (int)grid.x * 64, (int)grid.y * 64, n_out, c_in, dw, bws, bws ? db : nullptr);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
@@ -509,6 +771,19 @@ extern "C" int jatts_pack_conv_weight_split(const float* w, int32_t n_out, int32
   hipLaunchKernelGGL(wscale_kernel, dim3((unsigned)n_pad), dim3(256), 0, S_, w, n_out, c_in, k_w, mode, pn, inv);
   hipLaunchKernelGGL(pack_conv_weight_split_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, S_, w, n_out,
                      c_in, k_w, n_pad, c_pad, mode, inv, (f16*)out);
+  JATTS_CHECK_LAUNCH();
+  return JATTS_OK;
+}
+
+extern "C" int jatts_pack_conv_weight_bf16x3(const float* w, int32_t n_out, int32_t c_in, int32_t k_w, int32_t c_mult, int32_t dgrad, void* out, void* stream) {
+  if (!w || !out) return jatts_set_error_msg(JATTS_ERR_ARG, "pack_conv_weight_bf16x3: null pointer");
+  if (n_out < 1 || c_in < 1 || k_w < 1 || c_mult < 32 || c_mult % 32 != 0 || (dgrad != 0 && dgrad != 1))
+    return jatts_set_error_msg(JATTS_ERR_ARG, "pack_conv_weight_bf16x3: bad geometry (c_mult: a multiple of 32)");
+  const int pn = dgrad == 0 ? n_out : c_in, pc = dgrad == 0 ? c_in : n_out;
+  const int n_pad = (pn + 31) / 32 * 32, c_pad = (pc + c_mult - 1) / c_mult * c_mult;
+  const int64_t total = (int64_t)k_w * n_pad * (c_pad / 8);
+  hipLaunchKernelGGL(pack_conv_weight_bf16x3_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, S_, w, n_out, c_in,
+                     k_w, n_pad, c_pad, dgrad, (bf16*)out);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }

@@ -519,6 +519,22 @@ def pack_conv_weight_split_dev(w, c_mult=64, dgrad=False):
     return out, inv, c_pad
 
 
+def pack_conv_weight_bf16x3_dev(w, c_mult=64, dgrad=False):
+    """pack_conv_weight_bf16x3_k32 (the JATTS_F32E operand, jatts_conv_desc.w_layout = 1) as ONE HIP launch on a device f32 weight (n_out, c_in, k), for
+    weights that change every step (training): bit for bit the host packing.  dgrad=True packs the data-gradient operand W'[c][n][k-1-tap] directly.
+    -> (packed bf16, padded c_in of the packed conv)."""
+    lib = _abi.load()
+    w = _dev(w)
+    if w.dtype != torch.float32 or not w.is_contiguous():
+        w = w.float().contiguous()
+    n, c, k = w.shape
+    pn, pc = (c, n) if dgrad else (n, c)
+    n_pad, c_pad = round_up(pn, 32), round_up(pc, c_mult)
+    out = torch.empty(3 * k * n_pad * c_pad, dtype=torch.bfloat16, device=w.device)
+    _abi.check(lib.jatts_pack_conv_weight_bf16x3(w.data_ptr(), n, c, k, c_mult, int(dgrad), out.data_ptr(), _stream()), "jatts_pack_conv_weight_bf16x3")
+    return out, c_pad
+
+
 def convtranspose_as_conv(w, stride, padding):
     """ConvTranspose1d weight (c_in, c_out, K) -> polyphase Conv1d weight
     (stride*c_out, c_in, taps) + input offset `pad`, such that the conv output row j,
@@ -1157,9 +1173,13 @@ def masked_loss(rb, a, b, valid_len, kind, scale, log_offset=-1.0):
     return out
 
 
-def conv1d_wgrad(rb, x, dy, c_in, n_out, k_w, dil, pad, len_mul=1, want_db=False):
-    """-> dw (n_out, c_in, k_w); with want_db -> (dw, db): the bias gradient comes out of the same launch (the kernel's dy tiles)."""
+def conv1d_wgrad(rb, x, dy, c_in, n_out, k_w, dil, pad, len_mul=1, want_db=False, dtype=F32):
+    """-> dw (n_out, c_in, k_w); with want_db -> (dw, db): the bias gradient comes out of the same launch (the kernel's dy tiles).
+    dtype F32: the exact-f32 kernel; F32E: the emulated weight gradient (jatts_conv1d_wgrad_emul: k_w 1 / 3 / 5, halo <= 32 rows; any other geometry
+    takes the exact-f32 kernel inside the entry point)."""
     lib = _abi.load()
+    if dtype not in (F32, F32E):
+        raise ValueError("conv1d_wgrad: dtype F32 (exact) or F32E (three bf16 terms per operand, seven products)")
     dw = torch.empty(n_out, c_in, k_w, dtype=torch.float32, device=x.device)
     db = torch.empty(n_out, dtype=torch.float32, device=x.device) if want_db else None
     ws = torch.empty(rb.n_seq * (k_w * round_up(n_out, 64) * round_up(c_in, 64) + round_up(n_out, 64)), dtype=torch.float32,
@@ -1167,8 +1187,12 @@ def conv1d_wgrad(rb, x, dy, c_in, n_out, k_w, dil, pad, len_mul=1, want_db=False
     rg = rb.struct(len_mul)
     _count(2.0 * c_in * n_out * k_w * rb.total * len_mul)
     _ws(x.device)
-    _ws_check(lib.jatts_conv1d_wgrad(C.byref(rg), _dev(x).data_ptr(), x.shape[1], dy.data_ptr(), dy.shape[1], c_in, n_out, k_w, dil,
-                                      pad, dw.data_ptr(), _ptr(db), ws.data_ptr(), _stream()), "jatts_conv1d_wgrad")
+    if dtype == F32E:
+        _ws_check(lib.jatts_conv1d_wgrad_emul(C.byref(rg), _dev(x).data_ptr(), x.shape[1], dy.data_ptr(), dy.shape[1], c_in, n_out, k_w, dil,
+                                               pad, dtype, dw.data_ptr(), _ptr(db), ws.data_ptr(), _stream()), "jatts_conv1d_wgrad_emul")
+    else:
+        _ws_check(lib.jatts_conv1d_wgrad(C.byref(rg), _dev(x).data_ptr(), x.shape[1], dy.data_ptr(), dy.shape[1], c_in, n_out, k_w, dil,
+                                          pad, dw.data_ptr(), _ptr(db), ws.data_ptr(), _stream()), "jatts_conv1d_wgrad")
     return (dw, db) if want_db else dw
 
 

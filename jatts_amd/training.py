@@ -69,43 +69,93 @@ def split_convs(on=True):
         SPLIT_CONVS[0] = prev
 
 
+# precision="fp32_bf16x3" of the trainers (round 7): the same convs on the f32-EQUIVALENT emulated arithmetic (JATTS_F32E: three exact bf16 terms per
+# operand, seven partial products, csrc/conv1d_emul16.h) with the weight re-packed on the device every step (jatts_pack_conv_weight_bf16x3), and the WEIGHT
+# gradient on the same arithmetic where the dispatch rule below routes it (jatts_conv1d_wgrad_emul).  A switch of its own: SPLIT_CONVS / split_convs() keep
+# their meaning; with both on, the emulated mode wins.
+EMUL_CONVS = [False]
+
+# the trainers' precisions -> which contractions leave exact f32 (FastSpeech2Trainer.__init__ builds its error message from this)
+TRAIN_PRECISIONS = {
+    "fp32": "exact-f32 MFMA, the reference's arithmetic",
+    "fp32_split": "f32 tensors; the forward and data-gradient convs on split f16 hi / lo MFMA operands, everything else exact f32",
+    "fp32_bf16x3": "f32 tensors; the forward, data-gradient and weight-gradient convs on three exact bf16 terms per operand (seven partial products, "
+                   "f32-equivalent), everything else exact f32",
+}
+
+
+@contextlib.contextmanager
+def emul_convs(on=True):
+    prev, EMUL_CONVS[0] = EMUL_CONVS[0], bool(on)
+    try:
+        yield
+    finally:
+        EMUL_CONVS[0] = prev
+
+
+@contextlib.contextmanager
+def precision_convs(precision):
+    """The conv mode of a trainer precision around a step: split_convs() for "fp32_split", emul_convs() for "fp32_bf16x3"."""
+    with split_convs(precision == "fp32_split"), emul_convs(precision == "fp32_bf16x3"):
+        yield
+
+
+def emul_wgrad_wins(c_in, n_out, k, rows):
+    """Dispatch rule of the emulated weight gradient inside the trainers: True where jatts_conv1d_wgrad_emul measured faster than the exact-f32 kernel by more
+    than the run-to-run spread (profiles/r07_notes.md, "Weight gradient on the bf16 pipe": spread 0.1 - 5 %, one 9.5 % outlier).  That is the WIDE pointwise
+    class only -- k = 1 with n_out c_in >= 2^20 at >= 4 096 rows (2048 x 512: 1.16x); the 384-wide k = 1 / k = 3 shapes gain 4 - 6 %, inside the spread, and
+    k = 5 loses 13 - 16 %, so they stay on the exact-f32 kernel, the more accurate of the two.  A function of the launch's shape alone; no environment switch."""
+    return k == 1 and rows >= 4096 and n_out * c_in >= (1 << 20)
+
+
 class Conv1dFunction(torch.autograd.Function):
     """y = conv1d(x) on a packed ragged batch (rows, c_in) -> (rows, n_out), f32; "same"-style geometry via (dil, pad).
     forward: jatts_conv1d.  backward: dx = jatts_conv1d(dy, W'[c][n][k-1-tap], pad' = (k-1) dil - pad),
-    dW, db = jatts_conv1d_wgrad(x, dy) (the bias gradient falls out of the staged dy tiles)."""
+    dW, db = jatts_conv1d_wgrad(x, dy) (the bias gradient falls out of the staged dy tiles).
+    Three modes: exact f32, split (SPLIT_CONVS) and emulated (EMUL_CONVS); mode 0 / 1 / 2 travels in ctx.geom."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, rb, dil, pad):
         n_out, c_in, k = weight.shape
-        split = SPLIT_CONVS[0] and (k - 1) * dil <= 32        # (beyond the split kernel's tiles: the exact-f32 kernel)
-        if split:
-            wp, winv, c_pad = hip.pack_conv_weight_split_dev(weight.detach())
+        fits = (k - 1) * dil <= 32                            # (beyond the split / emulated kernels' tiles: the exact-f32 kernel)
+        emul = EMUL_CONVS[0] and fits
+        split = SPLIT_CONVS[0] and fits and not emul
+        winv, layout, code = None, 0, hip.F32
+        if emul:
+            (wp, c_pad), layout, code = hip.pack_conv_weight_bf16x3_dev(weight.detach()), 1, hip.F32E
+        elif split:
+            (wp, winv, c_pad), code = hip.pack_conv_weight_split_dev(weight.detach()), hip.F32S
         else:
-            (wp, c_pad), winv = hip.pack_conv_weight_dev(weight.detach(), hip.F32), None
+            wp, c_pad = hip.pack_conv_weight_dev(weight.detach(), hip.F32)
         xin = x.contiguous() if c_in == c_pad else hip.affine_cast(x.contiguous(), hip.F32, ldy=c_pad)
-        y = hip.conv1d(rb, xin, wp, c_pad, n_out, k, dtype=hip.F32S if split else hip.F32, dil=dil, pad=pad,
-                       bias=None if bias is None else bias.detach().contiguous(), w_inv=winv, out_f32=True)
+        y = hip.conv1d(rb, xin, wp, c_pad, n_out, k, dtype=code, dil=dil, pad=pad,
+                       bias=None if bias is None else bias.detach().contiguous(), w_inv=winv, out_f32=True, w_layout=layout)
         ctx.save_for_backward(x, weight)
-        ctx.geom = (rb, dil, pad, bias is not None, split)
+        ctx.geom = (rb, dil, pad, bias is not None, 2 if emul else 1 if split else 0, EMUL_CONVS[0])
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        rb, dil, pad, has_bias, split = ctx.geom
+        rb, dil, pad, has_bias, mode, emul_on = ctx.geom
         n_out, c_in, k = weight.shape
         dy = dy.contiguous().float()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            if split:      # the data gradient is a conv like the forward: same split arithmetic (the WEIGHT gradient below stays exact f32)
-                wp, winv, c_pad = hip.pack_conv_weight_split_dev(weight.detach(), dgrad=True)
+            winv, layout, code = None, 0, hip.F32
+            if mode == 2:    # the data gradient is a conv like the forward: same arithmetic
+                (wp, c_pad), layout, code = hip.pack_conv_weight_bf16x3_dev(weight.detach(), dgrad=True), 1, hip.F32E
+            elif mode == 1:  # (split: the WEIGHT gradient below stays exact f32)
+                (wp, winv, c_pad), code = hip.pack_conv_weight_split_dev(weight.detach(), dgrad=True), hip.F32S
             else:
-                (wp, c_pad), winv = hip.pack_conv_weight_dev(weight.detach(), hip.F32, dgrad=True), None       # W'[c][n][k-1-tap], packed in one launch
+                wp, c_pad = hip.pack_conv_weight_dev(weight.detach(), hip.F32, dgrad=True)       # W'[c][n][k-1-tap], packed in one launch
             dyp = dy if n_out == c_pad else hip.affine_cast(dy, hip.F32, ldy=c_pad)
-            dx = hip.conv1d(rb, dyp, wp, c_pad, c_in, k, dtype=hip.F32S if split else hip.F32, dil=dil, pad=(k - 1) * dil - pad, w_inv=winv, out_f32=True)
+            dx = hip.conv1d(rb, dyp, wp, c_pad, c_in, k, dtype=code, dil=dil, pad=(k - 1) * dil - pad, w_inv=winv, out_f32=True, w_layout=layout)
         want_db = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
-            dw = hip.conv1d_wgrad(rb, x.detach().contiguous().float(), dy, c_in, n_out, k, dil, pad, want_db=want_db)
+            # emulated mode: the weight gradient on the same arithmetic where the shape rule says it is the faster kernel (a halo beyond 32 rows never is)
+            wcode = hip.F32E if emul_on and (k - 1) * dil <= 32 and emul_wgrad_wins(c_in, n_out, k, x.shape[0]) else hip.F32
+            dw = hip.conv1d_wgrad(rb, x.detach().contiguous().float(), dy, c_in, n_out, k, dil, pad, want_db=want_db, dtype=wcode)
             if want_db:
                 dw, db = dw
         elif want_db:
@@ -205,9 +255,8 @@ class FastSpeech2Trainer:
     def __init__(self, model, lr=0.0008, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_norm=1.0, warmup_steps=4000, group=None,
                  bucket_bytes=64 << 20, overlap=True, gradient_accumulate_steps=1, scheduler="warmuplr", scheduler_params=None, capture_graph=False,
                  max_graphs=8, precision="fp32"):
-        if precision not in ("fp32", "fp32_split"):
-            raise ValueError("trainer precision: 'fp32' (exact-f32 MFMA, the reference's arithmetic) or 'fp32_split' (f32 tensors; the forward and "
-                             "data-gradient convs on split f16 hi / lo MFMA operands, everything else exact f32)")
+        if precision not in TRAIN_PRECISIONS:
+            raise ValueError(f"trainer precision {precision!r}: " + " or ".join(f"{k!r} ({v})" for k, v in TRAIN_PRECISIONS.items()))
         self.precision = precision
         self.model, self.base_lr, self.betas, self.eps, self.wd = model, lr, betas, eps, weight_decay
         self.grad_norm, self.warmup_steps, self.group, self.bucket_bytes = grad_norm, warmup_steps, group, bucket_bytes
@@ -405,7 +454,7 @@ class FastSpeech2Trainer:
 
     @torch.no_grad()
     def eval_step(self, batch):
-        with split_convs(self.precision == "fp32_split"):
+        with precision_convs(self.precision):
             return self._eval_step(batch)
 
     def _eval_step(self, batch):
@@ -566,7 +615,7 @@ class FastSpeech2Trainer:
         return out
 
     def train_step(self, batch):
-        with split_convs(self.precision == "fp32_split"):
+        with precision_convs(self.precision):
             return self._train_step_any(batch)
 
     def _train_step_any(self, batch):

@@ -2,7 +2,7 @@
 """One-GPU timing of FastSpeech2Trainer.train_step at the recipe's shape: conf/fastspeech2.v1.yaml model,
 batch_size 32, 128 phonemes x 6 frames per utterance, synthetic weights / targets.  Prints one JSON line; --shapes adds the
 per-kernel-family table from HIP-event records.
-    python tools/bench_train.py [--steps 5] [--batch 32]"""
+    python tools/bench_train.py [--steps 5] [--batch 32] [--precision fp32|fp32_split|fp32_bf16x3]"""
 import argparse
 import json
 import os
@@ -24,6 +24,7 @@ def main():
     ap.add_argument("--t-text", type=int, default=128)
     ap.add_argument("--frames", type=int, default=6)
     ap.add_argument("--model", default="fs2", choices=["fs2", "matcha"], help="matcha = tts1 MatchaTTS (matcha_tts.v1.prior.steplr.large.yaml)")
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "fp32_split", "fp32_bf16x3"], help="the trainer's precision (jatts_amd/training.py)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.model == "fs2":
@@ -42,7 +43,7 @@ def main():
                  durations=ds, duration_lens=il, pitch=torch.randn(B, T, 1, generator=g), pitch_lens=il,
                  energys=torch.randn(B, T, 1, generator=g), energy_lens=il)
     batch = {k: v.to(dev) if k in ("xs", "ys", "durations", "pitch", "energys") else v for k, v in batch.items()}
-    tr = (FastSpeech2Trainer if a.model == "fs2" else MatchaTTSTrainer)(m, lr=1e-4, grad_norm=1.0, warmup_steps=0)
+    tr = (FastSpeech2Trainer if a.model == "fs2" else MatchaTTSTrainer)(m, lr=1e-4, grad_norm=1.0, warmup_steps=0, precision=a.precision)
     l0 = float(tr.train_step(batch)["loss"])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -51,7 +52,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     frames = int(ol.sum())
-    print(json.dumps({"workload": f"{'FastSpeech2 v1' if a.model == 'fs2' else 'MatchaTTS (tts1)'} train step, batch {B} x {T} phonemes x {a.frames} frames", "ms_per_step": dt * 1e3,
+    print(json.dumps({"workload": f"{'FastSpeech2 v1' if a.model == 'fs2' else 'MatchaTTS (tts1)'} train step, batch {B} x {T} phonemes x {a.frames} frames", "precision": a.precision, "ms_per_step": dt * 1e3,
                       "frames_per_s": frames / dt, "loss_first": l0, "loss_last": float(out["loss"]),
                       "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30}))
 
