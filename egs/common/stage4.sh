@@ -3,7 +3,8 @@
 # reference's variables set: expdir, checkpoint, test_set, token_column, verbose, n_gpus
 # (reference egs/jsut/tts1/run.sh:237-260) and, optionally, decode_sets: the csv names under data/ to decode (default: the test set;
 # the hificaptain recipes also decode dev_raw_feat, reference egs/hificaptain_jp_female/tts1/run.sh:228).  One difference, additive: n_gpus > 1 is honoured (the reference
-# forces 1) -- every rank decodes its own shard of the csv, one process per GPU.
+# forces 1) -- every rank decodes its own shard of the csv, one process per GPU.  attention_precision (optional recipe variable): passed on as
+# --attention-precision when set.
 # shellcheck disable=SC2154
 stage4_decode() {
     # shellcheck disable=SC2012
@@ -36,6 +37,7 @@ stage4_decode() {
             --precision "${precision}" \
             --batch-size "${decode_batch_size}" \
             --n_gpus "${n_gpus}" \
+            ${attention_precision:+--attention-precision "${attention_precision}"} \
             --verbose "${verbose}" > "${outdir}/${name}/decode.log" 2>&1 || { tail -20 "${outdir}/${name}/decode.log"; exit 1; }
         log "Successfully finished decoding of ${name} set."
     done

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define JATTS_ABI_VERSION 6   /* 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
+#define JATTS_ABI_VERSION 7   /* 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
                                 * so every descriptor that embeds it (jatts_conv_desc, jatts_resunit_desc, jatts_resblock_desc, jatts_relattn_desc) shifted by 8 bytes; JATTS_F32E; 2 (round 4): jatts_conv_desc + w_inv / act_a / act_b, jatts_resunit_desc + ws1 / ws2, jatts_resblock_desc + ws1 / ws2;
                                 * bumped whenever a descriptor's layout or an entry point's signature changes: a stale library is refused at load */
 
@@ -489,6 +489,10 @@ int jatts_hifigan_output(const jatts_ragged* rg, int32_t dtype, const void* cons
  * ------------------------------------------------------------------------------- */
 typedef struct jatts_relattn_desc {
   jatts_ragged rg;
+  /* JATTS_F16 (f16 tensors), JATTS_F32 (exact f32), JATTS_F32S (f32 tensors, split f16 operands with block scales), or -- ABI 7 -- JATTS_F32E: f32
+   * tensors in the JATTS_F32 layout, K / V^T split into their three bf16 planes while they are staged into LDS, Q and P split in registers, both
+   * contractions as seven partial products on v_mfma_f32_16x16x32_bf16 (leading and small products in separate f32 accumulators; S joined per key tile,
+   * O at the end, one f32 add each); biases, rel_shift, scale, mask and the softmax stay exact f32.  JATTS_F32E6 is refused (JATTS_ERR_UNSUPPORTED). */
   int32_t dtype;
   int32_t n_heads;
   int32_t d_k;

@@ -163,6 +163,9 @@ def get_parser():
                         "tensors, convs and fused vocoder units on error-corrected split f16 hi/lo MFMA operands; fp32_bf16x3 = f32 tensors, the "
                         "same kernels on three exact bf16 terms per operand and seven MFMA products (a one-term contraction within 2 x an f32 FMA's error "
                         "bound for every input); fp32_bf16x3_6p = six products (extensions)")
+    p.add_argument("--attention-precision", default=None, choices=["fp32", "fp32_bf16x3"],
+                   help="arithmetic of the self-attention products, a switch of its own (f32 precisions only).  Absent = what --precision has always "
+                        "meant; fp32_bf16x3 = the seven-product bf16x3 attention kernel where it wins; fp32 = exact f32 (extension)")
     p.add_argument("--plot", action="store_true", help="also write <outdir>/outs/<id>.png like the reference")
     p.add_argument("--n_gpus", "--n-gpus", dest="n_gpus", type=int, default=1,
                    help="one process per GPU, every rank decodes its own shard of the csv (extension; the recipes' n_gpus). "
@@ -208,7 +211,8 @@ def main(argv=None):
     model_class = getattr(jatts_amd.models, config["model_type"])          # tts_decode.py:139
     model = model_class(**config["model_params"])
     model.load_state_dict(torch.load(args.checkpoint, map_location="cpu")["model"])
-    model = model.eval().to(device).set_precision(args.precision)
+    model = model.eval().to(device)
+    model = model.set_precision(args.precision) if args.attention_precision is None else model.set_precision(args.precision, attention=args.attention_precision)
     logging.info(f"Loaded model parameters from {args.checkpoint}.")
 
     stats = read_stats(args.stats, config["out_feat_type"])                # tts_decode.py:160-164

@@ -7,6 +7,7 @@
 // in-lane adds plus two cross-lane steps (xor 16, 32), and the probabilities are already
 // in B-operand position for O^T += V^T P^T -- no LDS round trip for P.
 #include "common.h"
+#include "resunit_emul16_impl.h"   // acc2x4 / mma16p: the seven-product rule of the emulated convs, shared with the bf3p<7> attention below
 
 namespace {
 
@@ -16,6 +17,11 @@ template <typename T> struct V8 { typedef typename Elem<T>::vec8 type; };
 // f16s (JATTS_F32S, round 4): f32 in memory, split into hi / lo f16 planes on the way into LDS / into the MFMA operand registers.
 template <typename T> struct G { typedef T type; typedef typename Elem<T>::vec8 vec8; static constexpr bool split = false; };
 template <> struct G<f16s> { typedef float type; typedef f32x8 vec8; static constexpr bool split = true; };
+// bf3 (JATTS_F32E, round 8): f32 in memory, the three exact bf16 planes in LDS / in the MFMA operand registers (common.h: bf3p<7>).  Not `split`: the
+// bf16 terms carry f32's exponent, so there is no power-of-two scale and no block maximum anywhere -- a tile is loaded, masked and stored like an f32 one.
+template <> struct G<bf3> { typedef float type; typedef f32x8 vec8; static constexpr bool split = false; };
+template <typename T> struct IsEmul { static constexpr bool value = false; };
+template <> struct IsEmul<bf3> { static constexpr bool value = true; };
 
 template <typename T>
 __device__ __forceinline__ typename G<T>::vec8 load8(const typename G<T>::type* p) {
@@ -55,6 +61,7 @@ __device__ __forceinline__ TG load1_buf(__amdgpu_buffer_rsrc_t rs, unsigned voff
 template <typename T>
 __device__ __forceinline__ typename Elem<T>::vec8 lds8(const char* p) {
   if constexpr (G<T>::split) return f16sx8{*reinterpret_cast<const f16x8*>(p), *reinterpret_cast<const f16x8*>(p + 16)};
+  else if constexpr (IsEmul<T>::value) return Vec8IO<T>::lds(p);     // one planar unit: 16 B of b0 | b1 | b2
   else return load8<T>(reinterpret_cast<const T*>(p));
 }
 // 8 f32 values, scaled by the power of two `sc`, as a split operand
@@ -98,12 +105,27 @@ __device__ __forceinline__ float attn_exp2i(int s) { return __uint_as_float((uns
 #endif
 constexpr int KB = 64;  // keys per tile
 
+// bf3p<7> fragment pair: the seven partial products, smallest first (mma16p: the order of common.h's mma32) -- six into `small`, the leading one into `big`
+using ::mma16;    // (the overloads of common.h stay visible next to this one)
+__device__ __forceinline__ void mma16(const bf3px8<7>& a, const bf3px8<7>& b, acc2x4& c) {
+  mma16p<0>(a, b, c); mma16p<1>(a, b, c); mma16p<2>(a, b, c); mma16p<3>(a, b, c); mma16p<4>(a, b, c); mma16p<5>(a, b, c); mma16p<6>(a, b, c);
+}
+__device__ __forceinline__ void acc16_zero(f32x4& a) { a = f32x4{0.f, 0.f, 0.f, 0.f}; }
+__device__ __forceinline__ void acc16_zero(acc2x4& a) { a.big = a.small = f32x4{0.f, 0.f, 0.f, 0.f}; }
+// the flash rescale of an output accumulator: both halves of a two-accumulator fragment take the same factor
+__device__ __forceinline__ void acc16_mul(f32x4& a, int r, float x) { a[r] *= x; }
+__device__ __forceinline__ void acc16_mul(acc2x4& a, int r, float x) { a.big[r] *= x; a.small[r] *= x; }
+
 template <typename T>
 __device__ __forceinline__ void store8(char* p, const typename G<T>::vec8& v, float sc = 1.f) {
   if constexpr (G<T>::split) {
     const f16sx8 o = split8(v, sc);
     *reinterpret_cast<f16x8*>(p) = o.hi;
     *reinterpret_cast<f16x8*>(p + 16) = o.lo;
+  } else if constexpr (IsEmul<T>::value) {
+    bf3px8<7> o;
+    bf3_split8(v, o);
+    Vec8IO<T>::sts(p, o);
   } else if (sizeof(T) == 2) {
     *reinterpret_cast<typename Elem<T>::vec8*>(p) = v;
   } else {
@@ -195,6 +217,24 @@ __device__ __forceinline__ void tile_store(const TileRegs<T, DK, KBT, NW>& tr, c
         for (int e = 0; e < 8; ++e)
           if (c0 + e >= mask_from) z[e] = from_f32<TG>(0.f);
       }
+      if constexpr (IsEmul<T>::value) {
+        // bf3: the V^T plane image is stored in the KEY ORDER OF THE P OPERAND.  Lane group g of 32-key block kb contracts keys 32 kb + 4 g + {0..3} (score
+        // fragment 2 kb) then 32 kb + 16 + 4 g + {0..3} (fragment 2 kb + 1) -- unit 4 kb + g of a channel row holds exactly those eight, per plane, so the
+        // P V fragment read is one planar unit like K's and P never goes through LDS.  A chunk's keys c0 .. c0 + 3 and c0 + 4 .. c0 + 7 are two 8-byte
+        // halves of two neighbouring units.
+        bf3px8<7> o;
+        bf3_split8(z, o);
+        char* vrow = vs + (size_t)(u / (KBT / 8)) * VP;
+        const int c0 = 8 * (u % (KBT / 8));
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          const int c = c0 + 4 * hf;
+          char* q = vrow + (size_t)(4 * (c >> 5) + ((c & 15) >> 2)) * 48 + (size_t)((c >> 4) & 1) * 8;
+          *reinterpret_cast<bf16x4*>(q) = bf16x4{o.b0[4 * hf], o.b0[4 * hf + 1], o.b0[4 * hf + 2], o.b0[4 * hf + 3]};
+          *reinterpret_cast<bf16x4*>(q + 16) = bf16x4{o.b1[4 * hf], o.b1[4 * hf + 1], o.b1[4 * hf + 2], o.b1[4 * hf + 3]};
+          *reinterpret_cast<bf16x4*>(q + 32) = bf16x4{o.b2[4 * hf], o.b2[4 * hf + 1], o.b2[4 * hf + 2], o.b2[4 * hf + 3]};
+        }
+      } else
       store8<T>(vs + (size_t)(u / (KBT / 8)) * VP + (size_t)(u % (KBT / 8)) * 8 * sizeof(T), z, sv);
     }
   }
@@ -210,11 +250,12 @@ __device__ __forceinline__ void tile_store(const TileRegs<T, DK, KBT, NW>& tr, c
 // NW = 8: 512-thread workgroups of 128 queries, one per CU (the same two waves per SIMD): a K / V^T tile is staged once for twice the
 // MFMA work and each thread holds half as much of it, so the whole next tile pair fits in registers again (full prefetch at d_k 256).
 template <typename T, int DK, int KBT, bool REL = true, int NW = 4>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) == 2) || KBT == 32) ? 2 : 1)) void relattn_kernel(jatts_relattn_desc d) {
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : IsEmul<T>::value ? ((DK == 96 || DK > 128) ? 1 : 2) : (((DK <= 256 && sizeof(T) == 2) || KBT == 32) ? 2 : 1)) void relattn_kernel(jatts_relattn_desc d) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef typename Elem<T>::vec8 Vec;
   typedef typename G<T>::type TG;          // element type in HBM (f32 for the split arithmetic)
   constexpr bool SPLIT = G<T>::split;
+  constexpr bool EMUL = IsEmul<T>::value;  // bf3: f32 in HBM, three bf16 planes in LDS (K as staged, V^T in the P operand's key order: tile_store), seven products
   // K tile pitch: the score MFMAs read 16 key rows x 4 channel groups per ds_read_b128; with the pitch = 2 (mod 4)
   // 16-byte units the hardware's 16-lane groups hit 16 distinct slots (+16 left 41 % of the LDS cycles in conflict)
   constexpr int KP = DK * (int)sizeof(T) + (sizeof(T) == 2 ? 32 : 16);
@@ -287,14 +328,19 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) ==
     const float sq = attn_exp2i(eq);
 #pragma unroll
     for (int s = 0; s < NKS; ++s) qf[s] = split8(qr[s], sq);
+  } else if constexpr (EMUL) {      // split once per workgroup, held in registers for every key tile
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) bf3_split8(load8<T>(qg + 32 * s + 8 * g), qf[s]);
   } else {
 #pragma unroll
     for (int s = 0; s < NKS; ++s) qf[s] = load8<T>(qg + 32 * s + 8 * g);
   }
 
-  f32x4 ot[NDF];
+  // bf3: leading | small products of O in separate accumulators for the WHOLE key loop (both take the same flash rescale factor), joined by one
+  // correctly rounded f32 add at the END, in front of the 1 / sum
+  typename Acc16<T>::type ot[NDF];
 #pragma unroll
-  for (int f = 0; f < NDF; ++f) ot[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int f = 0; f < NDF; ++f) acc16_zero(ot[f]);
   float m_run = -INFINITY, l_run = 0.f;
 
   // rel-pos bias rows of this lane's query (legacy rel_shift reads row qi for j <= qi, row qi + 1 beyond)
@@ -307,7 +353,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) ==
   // DMA_OK (JATTS_ATTN_DMA >= 2: every exact-f32 32-key-tile kernel, not only the bias-free d_k 256 one): tiles by LDS-direct loads in the half-tile
   // schedule below; nothing is staged in registers, so there is nothing to prefetch into
   constexpr bool DMA_OK = sizeof(T) == 4 && !SPLIT && KBT == 32 && NW == 4 && DK % 64 == 0 && (JATTS_ATTN_DMA >= 2 || (JATTS_ATTN_DMA == 1 && !REL && DK == 256));
-  constexpr bool PREFETCH = !DMA_OK && (NW == 8 || ((DK <= 192 || sizeof(T) != 2) && !(KBT == 32 && DK > 192)));   // (f32 d_k 256 at two workgroups per CU: no registers for it either)
+  constexpr bool PREFETCH = !DMA_OK && (NW == 8 || EMUL || ((DK <= 192 || sizeof(T) != 2) && !(KBT == 32 && DK > 192)));   // (f32 d_k 256 at two workgroups per CU: no registers for it either)
   // Without the registers for a whole tile pair (plain operands only): HALF a tile in flight at a time.  V^T(t) is loaded under the score
   // MFMAs of tile t and lands in LDS before P V; K(t+1) is loaded under P V(t) and lands after it -- each global round trip behind one
   // MFMA phase, the same two barriers per tile, 32 staging registers instead of 64 (f32 d_k 256 at two workgroups per CU waited on
@@ -443,9 +489,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) ==
     }
 
     // ---- S^T fragments: st[f][r] = key (j0 + 16 f + 4 g + r)  x  query qc ----
-    f32x4 st[NF];
+    typename Acc16<T>::type sta[NF];    // (bf3: leading | small products, joined per tile by the one add below -- the softmax works on plain f32 scores)
 #pragma unroll
-    for (int f = 0; f < NF; ++f) st[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int f = 0; f < NF; ++f) acc16_zero(sta[f]);
     if constexpr (PIPE_S) {           // fragment i + 1 is read while fragment i's MFMAs issue (see PIPE_S above)
       auto kfrag = [&](int i) { return lds8<T>(ks + (size_t)(16 * (i % NF) + qc) * KP + (size_t)(32 * (i / NF) + 8 * g) * sizeof(T)); };
       Vec a0 = kfrag(0);
@@ -454,7 +500,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) ==
         Vec a1 = a0;
         if (i + 1 < NKS * NF) a1 = kfrag(i + 1);
         __builtin_amdgcn_sched_barrier(0);
-        mma16(a0, qf[i / NF], st[i % NF]);
+        mma16(a0, qf[i / NF], sta[i % NF]);
         __builtin_amdgcn_sched_barrier(0);
         a0 = a1;
       }
@@ -464,9 +510,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) ==
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
           const Vec a = lds8<T>(ks + (size_t)(16 * f + qc) * KP + (size_t)(32 * s + 8 * g) * sizeof(T));
-          mma16(a, qf[s], st[f]);
+          mma16(a, qf[s], sta[f]);
         }
       }
+    }
+    f32x4 st[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      acc16_finish(sta[f]);
+      st[f] = acc16_val(sta[f]);
     }
     // ---- bias terms, scale, mask, online softmax ----
     float mx = -INFINITY;
@@ -508,7 +560,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) ==
 #pragma unroll
     for (int f = 0; f < NDF; ++f)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) ot[f][r] *= oscale;
+      for (int r = 0; r < 4; ++r) acc16_mul(ot[f], r, oscale);
     }
 
     if constexpr (DMA) {
@@ -538,6 +590,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) ==
 #pragma unroll
         for (int r = 0; r < 4; ++r) { pv[r] = st[2 * kb][r]; pv[4 + r] = st[2 * kb + 1][r]; }
         pb = split8(pv, 32768.f);
+      } else if constexpr (EMUL) {    // P in [0, 1]: its three bf16 terms are exact, no scale
+        f32x8 pv;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { pv[r] = st[2 * kb][r]; pv[4 + r] = st[2 * kb + 1][r]; }
+        bf3_split8(pv, pb);
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -584,6 +641,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) ==
           const f16x4 h1 = *reinterpret_cast<const f16x4*>(p1), l1 = *reinterpret_cast<const f16x4*>(p1 + 16);
 #pragma unroll
           for (int r = 0; r < 4; ++r) { a.hi[r] = h0[r]; a.hi[4 + r] = h1[r]; a.lo[r] = l0[r]; a.lo[4 + r] = l1[r]; }
+        } else if constexpr (EMUL) {  // unit 4 kb + g of the channel row already holds this lane's eight keys (tile_store)
+          a = lds8<T>(vs + (size_t)(16 * f + qc) * VP + (size_t)(4 * kb + g) * 48);
         } else {
           const T* vr = reinterpret_cast<const T*>(vs + (size_t)(16 * f + qc) * VP) + 32 * kb + 4 * g;
 #pragma unroll
@@ -609,9 +668,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : (((DK <= 256 && sizeof(T) ==
     const float inv = (SPLIT ? attn_exp2i(-(15 + ev_prev)) : 1.f) / l_run;
     TG* og = (TG*)d.out + (int64_t)(row0 + qi) * d.ldo + h * DK;
 #pragma unroll
-    for (int f = 0; f < NDF; ++f)
+    for (int f = 0; f < NDF; ++f) {
+      acc16_finish(ot[f]);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) og[16 * f + 4 * g + r] = from_f32<TG>(ot[f][r] * inv);
+      for (int r = 0; r < 4; ++r) og[16 * f + 4 * g + r] = from_f32<TG>(acc16_val(ot[f])[r] * inv);
+    }
   }
 }
 
@@ -630,7 +691,13 @@ int launch_attn_kb(const jatts_relattn_desc& d, hipStream_t s) {
 template <typename T, int DK>
 int launch_attn(const jatts_relattn_desc& d, hipStream_t s) {
   // f32 / split operands at d_k >= 128: 32-key tiles, two workgroups per CU (FastSpeech2 text2mel 39.8 -> 37.4 ms: profiles/r03_notes.md)
-  if constexpr (sizeof(T) == 4 && DK >= 128 && DK % 64 == 0) {
+  if constexpr (IsEmul<T>::value) {
+    // bf3: three bf16 planes are 6 B per element, a K + V^T tile pair 12 KBT d_k bytes (+ pitch padding).  64-key tiles up to d_k 96 (24 / 49 / 74 KB: 6 / 3 /
+    // 2 workgroups per CU by LDS), 32-key tiles above (d_k 128 49 KB, 192 74 KB, 256 98 KB).  Four waves everywhere, the whole next tile pair prefetched in
+    // registers; d_k 192 / 256 hold 72 / 96 registers of split Q and 96 / 128 of the two O accumulators per lane and take one wave per SIMD (417 / 506
+    // registers), and so does d_k 96 (314: at the two-wave budget of 256 it spilled inside the key loop); d_k 32 / 64 / 128 keep two (tools/kernel_resources.py).
+    return launch_attn_kb<T, DK, (DK <= 96 ? KB : 32), true, 4>(d, s);
+  } else if constexpr (sizeof(T) == 4 && DK >= 128 && DK % 64 == 0) {
     // d_k 256: the split arithmetic takes 512-thread workgroups (half the hi / lo conversion work per wave, the whole next tile pair
     // prefetched: T = 768 511 -> 466 us); exact f32 is slower that way (738 -> 771 us: eight waves in lockstep on the barriers) and
     // keeps four waves with half a tile in flight.
@@ -688,6 +755,9 @@ extern "C" int jatts_relpos_attention(const jatts_relattn_desc* d, void* stream)
   if (d->dtype == JATTS_F16) return dispatch_dk<f16>(*d, s);
   if (d->dtype == JATTS_F32) return dispatch_dk<float>(*d, s);
   if (d->dtype == JATTS_F32S) return dispatch_dk<f16s>(*d, s);     // f32 tensors, split f16 hi / lo MFMA operands (round 4)
+  if (d->dtype == JATTS_F32E) return dispatch_dk<bf3>(*d, s);      // f32 tensors, three bf16 planes per operand, seven products on v_mfma_f32_16x16x32_bf16 (round 8)
+  if (d->dtype == JATTS_F32E6)
+    return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "relpos_attention: the emulated attention keeps seven partial products (JATTS_F32E); JATTS_F32E6 is not built");
   return jatts_set_error_msg(JATTS_ERR_ARG, "relpos_attention: unknown dtype");
 }
 

@@ -480,6 +480,60 @@ def split_weights(on=True):
         _SPLIT_WEIGHTS[0] = prev
 
 
+# Self-attention arithmetic, a switch of its own (the models' set_precision(precision, attention=...)).  None: what the precision name has always meant
+# (fp32_split: the split f16 attention; every other name: exact f32 / f16 with the tensors) -- bit for bit.  "fp32": exact f32.  "fp32_bf16x3": the
+# seven-product bf16x3 kernel (JATTS_F32E of jatts_relpos_attention) wherever emul_attention_wins says so, exact f32 elsewhere.
+ATTENTION_PRECISIONS = ("fp32", "fp32_bf16x3")
+ATTENTION_F32_PRECISIONS = ("fp32", "fp32_bf16x3", "fp32_bf16x3_6p", "fp32_split")     # the precisions whose activations are f32 tensors
+_ATTENTION = [None]
+
+
+def check_attention_precision(precision, attention):
+    """The models' set_precision argument check: raises ValueError for an unknown name or for an attention choice under f16 tensors."""
+    if precision not in PRECISIONS:
+        raise ValueError(precision)
+    if attention is None:
+        return
+    if attention not in ATTENTION_PRECISIONS:
+        raise ValueError(f"attention={attention!r}: None (what the precision implies) or one of {ATTENTION_PRECISIONS}")
+    if precision not in ATTENTION_F32_PRECISIONS:
+        raise ValueError(f"attention={attention!r} needs f32 activations: precision one of {ATTENTION_F32_PRECISIONS}, not {precision!r}")
+
+
+@contextlib.contextmanager
+def attention_precision(attention):
+    """Inside: ConformerRunner / Matcha's transformer blocks are built with this attention arithmetic (see ATTENTION_PRECISIONS).  Nests."""
+    prev, _ATTENTION[0] = _ATTENTION[0], attention
+    try:
+        yield
+    finally:
+        _ATTENTION[0] = prev
+
+
+def emul_attention_wins(n_heads, d_k, rel_mode):
+    """The ONE routing rule of attention="fp32_bf16x3": does the bf16x3 kernel beat the exact-f32 one for this launch family?  A function of the
+    head geometry and the bias mode only -- never of a length or a batch size, so an utterance alone, the same utterance inside a batch and a
+    replayed graph all take the same kernel.  The C ABI always honours the dtype it is given.
+
+    Round 8 (profiles/r08_attn_by_shape.txt, r08_notes.md): timed alternately against the exact-f32 kernel, the first bf16x3 kernel is SLOWER on every
+    launch the BASELINE configs make -- d_k 192 (FastSpeech2) 0.66 - 0.93 x, d_k 256 (Matcha) 0.57 - 0.68 x, d_k 96 (VITS text encoder) inside the 1 - 2 % run-to-run
+    spread at T = 128 and 0.71 x at T = 768; d_k 128 0.99 x.  Only d_k 64 at T = 768 came out ahead (1.12 x against a 10 % spread
+    of the exact-f32 timings in that session), a shape no config launches.  A shape inside the spread or slower stays on exact f32, so nothing is
+    routed yet: attention="fp32_bf16x3" is accepted, keyed and plumbed, and computes what attention="fp32" computes until a faster kernel earns a
+    True here."""
+    return False
+
+
+def attention_dtype(dtype, split, attention, n_heads, d_k, rel_mode):
+    """dtype code of one relpos_attention call of the inference path: `dtype` / `split` are the runner's tensors and fp32_split flag, `attention` its
+    attention choice (None = as the precision implies)."""
+    if attention is None or dtype != F32:
+        return F32S if split else dtype
+    if attention == "fp32_bf16x3" and emul_attention_wins(n_heads, d_k, rel_mode):
+        return F32E
+    return F32
+
+
 def f32_operand(w, c_mult=64):
     """A conv weight for `dtype=F32` call sites in the current weight mode: packed exact f32, SplitWeight or EmulWeight."""
     m = _SPLIT_WEIGHTS[0]

@@ -98,6 +98,7 @@ class ConformerRunner:
         RelPositionMultiHeadedAttention (VITS text encoder and decoder)."""
         self.dtype, self.device, self.H = dtype, device, n_heads
         self.split = dtype == hip.F32 and hip._SPLIT_WEIGHTS[0] == 1     # set_precision("fp32_split"): the attention takes the split arithmetic
+        self.attn = hip._ATTENTION[0]     # set_precision(..., attention=): None = as the precision implies (hip.attention_dtype)
         self.wmode = hip._SPLIT_WEIGHTS[0] if dtype == hip.F32 else 0    # the run-time packed position operands follow the weight mode
         self.rel_style = rel_style
         g = lambda k: sd[prefix + k]  # noqa: E731
@@ -224,7 +225,7 @@ class ConformerRunner:
                 hip.conv1d(rb, qk, heads[h], hip.round_up(dk, 64), n_pos, 1, dtype=self.dtype, bias=cv[h], ldx=2 * A,
                            x_col0=h * dk, out=g, out_ld=H * ldg, out_col0=h * ldg)
         ctx = hip.relpos_attention(rb, qk, 2 * A, qk, 2 * A, vt, ldvt, g, ldg, ku, 1.0 / math.sqrt(dk),
-                                   H, dk, hip.F32S if self.split else self.dtype, q_col0=0, k_col0=A, rel_mode=rel_mode, rel_center=rel_center, vt_col0=vcol,
+                                   H, dk, hip.attention_dtype(self.dtype, self.split, self.attn, H, dk, rel_mode), q_col0=0, k_col0=A, rel_mode=rel_mode, rel_center=rel_center, vt_col0=vcol,
                                    kv_len=kv_len)
         hip.conv1d(rb, ctx, L["o"].w, A, A, 1, dtype=self.dtype, bias=L["o"].b, resid=x, out=x, out_f32=True)
 

@@ -89,6 +89,7 @@ class _TBlock:
         f32 = lambda t: t.detach().float().to(dev).contiguous()  # noqa: E731
         self.heads = heads
         self.split = dt == hip.F32 and hip._SPLIT_WEIGHTS[0] == 1      # set_precision("fp32_split"): the attention takes the split arithmetic too
+        self.attn = hip._ATTENTION[0]     # set_precision(..., attention=): None = as the precision implies (hip.attention_dtype)
         self.n1 = (f32(sd[p + "norm1.weight"]), f32(sd[p + "norm1.bias"]))
         self.n3 = (f32(sd[p + "norm3.weight"]), f32(sd[p + "norm3.bias"]))
         wq, wk = sd[p + "attn1.to_q.weight"], sd[p + "attn1.to_k.weight"]
@@ -122,7 +123,7 @@ class _TBlock:
             qk = hip.conv1d(rb, n, self.qk.w, self.qk.c_in, 2 * I, 1, dtype=dt)
             vt = hip.conv1d(rb, n, self.v.w, self.v.c_in, I, 1, dtype=dt, transposed=True, out_ld=ldvt, y_seq_col0=vcol)
         a = hip.relpos_attention(rb, qk, 2 * I, qk, 2 * I, vt, ldvt, None, 0, key_bias, self.dh ** -0.5, self.heads,
-                                 self.dh, hip.F32S if self.split else dt, q_col0=0, k_col0=I, rel_mode=0, vt_col0=vcol)
+                                 self.dh, hip.attention_dtype(dt, self.split, self.attn, self.heads, self.dh, 0), q_col0=0, k_col0=I, rel_mode=0, vt_col0=vcol)
         hip.conv1d(rb, a, self.o.w, self.o.c_in, C, 1, dtype=dt, bias=self.o.b, resid=x, out=x, out_f32=True)
         n = hip.layernorm(x, self.n3[0], self.n3[1], dt, GN_EPS)
         # SnakeBeta rides in the epilogue of the conv that feeds it (one launch and one round trip of the widest tensor less)
@@ -248,6 +249,7 @@ class _MatchaBase(torch.nn.Module):
                                   enc_attn=transformer_enc_attn_dropout_rate, dur=duration_predictor_dropout_rate, decoder=decoder_dropout)
         self._train_calls = 0
         self.precision = "fp32"   # the reference's arithmetic; set_precision("fp16") selects the fast mode
+        self.attention = None     # set_precision(..., attention=): None = the attention arithmetic the precision implies
         self._prep = None
         self.eval()
 
@@ -258,14 +260,15 @@ class _MatchaBase(torch.nn.Module):
             self.requires_grad_(True)
         return self
 
-    def set_precision(self, precision):
+    def set_precision(self, precision, attention=None):
         # fp32_split: f32 tensors, every Conv1d / Linear but the duration predictor's on split f16 hi/lo MFMA operands (hip.SplitWeight;
         # csrc/conv1d_split.h); fp32_bf16x3 (fp32_bf16x3_6p): the same convs on three exact bf16 terms per operand, seven (six) partial products
         # per product (hip.EmulWeight; csrc/conv1d_emul.h)
-        if precision not in hip.PRECISIONS:
-            raise ValueError(precision)
-        if precision != self.precision:
-            self.precision, self._prep = precision, None
+        # attention: the self-attention products' arithmetic, a switch of its own.  None (default) = what `precision` has always meant; "fp32_bf16x3" =
+        # the seven-product bf16x3 kernel where hip.emul_attention_wins routes it; "fp32" = exact f32.  f32 activations only (not with "fp16").
+        hip.check_attention_precision(precision, attention)
+        if precision != self.precision or attention != self.attention:
+            self.precision, self.attention, self._prep = precision, attention, None
         return self
 
     def load_state_dict(self, *a, **k):
@@ -280,12 +283,12 @@ class _MatchaBase(torch.nn.Module):
         dev = self.encoder_proj.weight.device
         if dev.type != "cuda":
             raise hip._abi.JattsHipError("jatts_amd Matcha-TTS runs on the GPU only (no CPU fallback); call .to('cuda')")
-        key = (self.precision, str(dev))
+        key = (self.precision, self.attention, str(dev))
         if self._prep is not None and self._prep["key"] == key:
             return self._prep
         hip._abi.load()
         dt = hip.F16 if self.precision == "fp16" else hip.F32
-        with hip.split_weights(self.precision):
+        with hip.split_weights(self.precision), hip.attention_precision(self.attention):
             return self._prepare_packed(dev, key, dt)
 
     def _prepare_packed(self, dev, key, dt):

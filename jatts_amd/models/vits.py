@@ -137,6 +137,7 @@ class VITS(torch.nn.Module):
                                   dur=duration_predictor_dropout_rate, post=posterior_encoder_dropout_rate, flow=flow_dropout_rate)
         self._train_calls = 0
         self.precision = "fp32"   # the reference's arithmetic; set_precision("fp16") selects the fast mode
+        self.attention = None     # set_precision(..., attention=): None = the attention arithmetic the precision implies
         self._prep = None
         self.eval()
 
@@ -147,14 +148,15 @@ class VITS(torch.nn.Module):
             self.requires_grad_(True)
         return self
 
-    def set_precision(self, precision):
+    def set_precision(self, precision, attention=None):
         # fp32_split: f32 tensors, every Conv1d / Linear but the duration predictor's on split f16 hi/lo MFMA operands (hip.SplitWeight;
         # csrc/conv1d_split.h); fp32_bf16x3 (fp32_bf16x3_6p): the same convs on three exact bf16 terms per operand, seven (six) partial products
         # per product (hip.EmulWeight; csrc/conv1d_emul.h)
-        if precision not in hip.PRECISIONS:
-            raise ValueError(precision)
-        if precision != self.precision:
-            self.precision, self._prep = precision, None
+        # attention: the self-attention products' arithmetic, a switch of its own.  None (default) = what `precision` has always meant; "fp32_bf16x3" =
+        # the seven-product bf16x3 kernel where hip.emul_attention_wins routes it; "fp32" = exact f32.  f32 activations only (not with "fp16").
+        hip.check_attention_precision(precision, attention)
+        if precision != self.precision or attention != self.attention:
+            self.precision, self.attention, self._prep = precision, attention, None
         return self
 
     def load_state_dict(self, *a, **k):
@@ -169,12 +171,12 @@ class VITS(torch.nn.Module):
         dev = self.feat_out.weight.device
         if dev.type != "cuda":
             raise hip._abi.JattsHipError("jatts_amd.VITS runs on the GPU only (no CPU fallback); call .to('cuda')")
-        key = (self.precision, str(dev))
+        key = (self.precision, self.attention, str(dev))
         if self._prep is not None and self._prep["key"] == key:
             return self._prep
         hip._abi.load()
         dt = hip.F16 if self.precision == "fp16" else hip.F32
-        with hip.split_weights(self.precision):
+        with hip.split_weights(self.precision), hip.attention_precision(self.attention):
             return self._prepare_packed(dev, key, dt)
 
     def _prepare_packed(self, dev, key, dt):
