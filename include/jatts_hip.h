@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define JATTS_ABI_VERSION 7   /* 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
+#define JATTS_ABI_VERSION 7   /* (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
                                 * so every descriptor that embeds it (jatts_conv_desc, jatts_resunit_desc, jatts_resblock_desc, jatts_relattn_desc) shifted by 8 bytes; JATTS_F32E; 2 (round 4): jatts_conv_desc + w_inv / act_a / act_b, jatts_resunit_desc + ws1 / ws2, jatts_resblock_desc + ws1 / ws2;
                                 * bumped whenever a descriptor's layout or an entry point's signature changes: a stale library is refused at load */
 
@@ -455,6 +455,17 @@ double jatts_mfma_probe_flops(int32_t dtype, int32_t iters, int32_t workgroups);
 int jatts_bgemm(const float* a, int64_t sa_outer, int64_t sa_inner, int32_t lda, int32_t trans_a, const float* b, int64_t sb_outer,
                 int64_t sb_inner, int32_t ldb, int32_t trans_b, float* c, int64_t sc_outer, int64_t sc_inner, int32_t ldc, int32_t n_outer,
                 int32_t n_inner, int32_t m, int32_t n, int32_t k, float alpha, int32_t accumulate, void* stream);
+
+/* The same product on the f32-EQUIVALENT emulated arithmetic (round 10; the same reference lines: the torch.matmul calls of forward_attention and of
+ * LegacyRelPositionMultiHeadedAttention.forward, modules/transformer/attention.py:164-206, under autograd).  jatts_bgemm's arguments with their meaning
+ * unchanged, f32 in and out, plus `arith`: JATTS_F32E -- every f32 value of both operands is carried exactly as three bf16 terms (split while the tile is
+ * staged, no scales), seven of the nine partial products run on v_mfma_f32_16x16x32_bf16, the leading product and the six small ones in separate f32
+ * accumulators joined by one add per output; alpha and accumulate are applied after that add.  A one-term product is within 2^-23 of a b for every
+ * input.  JATTS_F32E6 is refused (JATTS_ERR_UNSUPPORTED); any other code is JATTS_ERR_ARG.  Deterministic: no split-K, no atomics, and an output's bits
+ * do not depend on the tile the dispatcher picks.  (Bits 8.. of `arith` are reserved for the tests' tile override and must be zero otherwise.) */
+int jatts_bgemm_emul(const float* a, int64_t sa_outer, int64_t sa_inner, int32_t lda, int32_t trans_a, const float* b, int64_t sb_outer,
+                     int64_t sb_inner, int32_t ldb, int32_t trans_b, float* c, int64_t sc_outer, int64_t sc_inner, int32_t ldc, int32_t n_outer,
+                     int32_t n_inner, int32_t m, int32_t n, int32_t k, float alpha, int32_t accumulate, int32_t arith, void* stream);
 
 /* Scratch of the DETERMINISTIC reductions of the training kernels (round 4): jatts_layernorm_bwd, jatts_groupnorm_bwd,
  * jatts_snakebeta_bwd, jatts_dwconv_wgrad, jatts_col_stats, jatts_col_sum, jatts_col_wsum, jatts_seq_sum, jatts_qkv_split_bwd,

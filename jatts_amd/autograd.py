@@ -269,13 +269,25 @@ class QKVSplit(torch.autograd.Function):
 class BMM(torch.autograd.Function):
     """Batched matmul of the attention products on the exact-f32 matrix pipe (jatts_bgemm; round 4: these were torch.matmul -> rocBLAS):
     c = a @ b (trans_b False: b (..., k, n)) or a @ b^T (trans_b True: b (..., n, k)); a is (O, I, m, k), b is (O, I, ., .) or (I, ., .) --
-    shared over O, as the position projection p_h is over the batch; its gradient is then summed over O."""
+    shared over O, as the position projection p_h is over the batch; its gradient is then summed over O.
+    Under training.emul_attention() each of the three products (forward, da, db) goes to the seven-product bf16x3 kernel (jatts_bgemm_emul) where
+    training.emul_bgemm_wins(m, n, k) says so for ITS dimensions; the three decisions are taken in forward and travel in ctx.codes, so backward
+    launches what forward decided whatever the context is by then."""
 
     @staticmethod
     def forward(ctx, a, b, trans_b):
+        from . import training      # (training imports the model code that imports this module)
         ctx.trans_b = bool(trans_b)
         ctx.save_for_backward(a, b)
-        return hip.bgemm(a, b, trans_b=ctx.trans_b)
+        m, k = a.shape[-2], a.shape[-1]
+        n = b.shape[-2] if ctx.trans_b else b.shape[-1]
+        if training.EMUL_ATTENTION[0]:
+            pick = lambda m_, n_, k_: hip.F32E if training.emul_bgemm_wins(m_, n_, k_) else hip.F32
+            # c: (m x n) over k | da = dc @ b^T or dc @ b: (m x k) over n | db = dc^T @ a: (n x k) over m, or a^T @ dc: (k x n) over m
+            ctx.codes = (pick(m, n, k), pick(m, k, n), pick(n, k, m) if ctx.trans_b else pick(k, n, m))
+        else:
+            ctx.codes = (hip.F32, hip.F32, hip.F32)
+        return hip.bgemm(a, b, trans_b=ctx.trans_b, dtype=ctx.codes[0])
 
     @staticmethod
     def backward(ctx, dc):
@@ -283,9 +295,10 @@ class BMM(torch.autograd.Function):
         dc = dc.contiguous()
         da = db = None
         if ctx.needs_input_grad[0]:
-            da = hip.bgemm(dc, b, trans_b=not ctx.trans_b)                       # dc @ b^T   |   dc @ b
+            da = hip.bgemm(dc, b, trans_b=not ctx.trans_b, dtype=ctx.codes[1])                       # dc @ b^T   |   dc @ b
         if ctx.needs_input_grad[1]:
-            db = hip.bgemm(dc, a, trans_a=True) if ctx.trans_b else hip.bgemm(a, dc, trans_a=True)   # dc^T @ a (n x k)  |  a^T @ dc (k x n)
+            # dc^T @ a (n x k)  |  a^T @ dc (k x n)
+            db = hip.bgemm(dc, a, trans_a=True, dtype=ctx.codes[2]) if ctx.trans_b else hip.bgemm(a, dc, trans_a=True, dtype=ctx.codes[2])
             if b.dim() == 3:
                 db = db.sum(0)
         return da, db, None

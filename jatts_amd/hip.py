@@ -1678,8 +1678,10 @@ def seq_sum(rb, x):
     return out
 
 
-def bgemm(a, b, trans_a=False, trans_b=False, alpha=1.0, out=None):
-    """jatts_bgemm: C[o][i] = alpha * op(a[o][i]) @ op(b[o][i]) on the exact-f32 matrix pipe (the training step's attention products).
+def bgemm(a, b, trans_a=False, trans_b=False, alpha=1.0, out=None, dtype=F32, _tile=0):
+    """jatts_bgemm: C[o][i] = alpha * op(a[o][i]) @ op(b[o][i]) on the exact-f32 matrix pipe (the training step's attention products), or with
+    dtype=F32E jatts_bgemm_emul: the same product, f32 in and out, on three exact bf16 terms per operand and seven partial products (f32-equivalent).
+    F32E6 has no batched GEMM and raises.  (_tile: tests only -- forces a tile of the emulated kernel, WNF | MF << 4.)
     a, b: f32 device tensors of 4 dims (O, I, rows, cols) -- any strides on the two batch dims, rows contiguous -- or 3 dims (I, rows, cols)
     = shared over O.  trans_a: a holds (k x m); trans_b: b holds (n x k).  -> (O, I, m, n) contiguous."""
     lib = _abi.load()
@@ -1708,6 +1710,13 @@ def bgemm(a, b, trans_a=False, trans_b=False, alpha=1.0, out=None):
           or out.device != a.device):
         raise ValueError(f"bgemm: out must be an f32 device tensor of shape {(O, ai, m, n)} with contiguous rows")
     _count(2.0 * O * ai * m * n * k)
+    if dtype != F32:
+        if dtype != F32E:
+            raise ValueError("bgemm: dtype is F32 (exact f32) or F32E (seven-product bf16x3); the six-product F32E6 has no batched GEMM")
+        with _Timed("bgemm_emul", (O * ai, m, n, k)):
+            _abi.check(lib.jatts_bgemm_emul(a.data_ptr(), sao, sai, lda, int(trans_a), b.data_ptr(), sbo, sbi, ldb, int(trans_b), out.data_ptr(), out.stride(0),
+                                            out.stride(1), out.stride(2), O, ai, m, n, k, float(alpha), 0, F32E | int(_tile) << 8, _stream()), "jatts_bgemm_emul")
+        return out
     with _Timed("bgemm", (O * ai, m, n, k)):
         _abi.check(lib.jatts_bgemm(a.data_ptr(), sao, sai, lda, int(trans_a), b.data_ptr(), sbo, sbi, ldb, int(trans_b), out.data_ptr(), out.stride(0),
                                    out.stride(1), out.stride(2), O, ai, m, n, k, float(alpha), 0, _stream()), "jatts_bgemm")

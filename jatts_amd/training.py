@@ -93,6 +93,32 @@ def emul_convs(on=True):
         EMUL_CONVS[0] = prev
 
 
+# attention="fp32_bf16x3" of the trainers (round 10): the attention products of autograd.BMM -- q k^T, q p^T, P v, the Gaussian-upsampling p_up @ hs and their
+# gradients -- on the same emulated arithmetic (jatts_bgemm_emul) where emul_bgemm_wins routes them.  A switch of its own, independent of the conv modes.
+EMUL_ATTENTION = [False]
+TRAIN_ATTENTIONS = {
+    "fp32": "exact-f32 MFMA (the default, also None)",
+    "fp32_bf16x3": "three exact bf16 terms per operand, seven partial products, for the product shapes emul_bgemm_wins routes; exact f32 elsewhere",
+}
+
+
+@contextlib.contextmanager
+def emul_attention(on=True):
+    prev, EMUL_ATTENTION[0] = EMUL_ATTENTION[0], bool(on)
+    try:
+        yield
+    finally:
+        EMUL_ATTENTION[0] = prev
+
+
+def emul_bgemm_wins(m, n, k):
+    """Dispatch rule of the emulated batched GEMM inside autograd.BMM: True only for the (m, n, k) classes where jatts_bgemm_emul measured faster than the
+    exact-f32 jatts_bgemm by more than the exact kernel's run-to-run spread; a shape inside the spread stays on exact f32, the more accurate of the two.
+    A function of the three GEMM dimensions alone: no batch size, no environment switch.  NO class has such a measurement yet (profiles/r10_notes.md), so
+    the rule routes nothing and attention="fp32_bf16x3" launches what "fp32" launches; the kernel stays reachable through hip.bgemm(dtype=hip.F32E)."""
+    return False
+
+
 @contextlib.contextmanager
 def precision_convs(precision):
     """The conv mode of a trainer precision around a step: split_convs() for "fp32_split", emul_convs() for "fp32_bf16x3"."""
@@ -254,10 +280,13 @@ class FastSpeech2Trainer:
 
     def __init__(self, model, lr=0.0008, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_norm=1.0, warmup_steps=4000, group=None,
                  bucket_bytes=64 << 20, overlap=True, gradient_accumulate_steps=1, scheduler="warmuplr", scheduler_params=None, capture_graph=False,
-                 max_graphs=8, precision="fp32"):
+                 max_graphs=8, precision="fp32", attention=None):
         if precision not in TRAIN_PRECISIONS:
             raise ValueError(f"trainer precision {precision!r}: " + " or ".join(f"{k!r} ({v})" for k, v in TRAIN_PRECISIONS.items()))
+        if attention is not None and attention not in TRAIN_ATTENTIONS:
+            raise ValueError(f"trainer attention {attention!r}: None or " + " or ".join(f"{k!r} ({v})" for k, v in TRAIN_ATTENTIONS.items()))
         self.precision = precision
+        self.attention = attention      # the attention products' arithmetic, independent of `precision` (emul_attention / emul_bgemm_wins)
         self.model, self.base_lr, self.betas, self.eps, self.wd = model, lr, betas, eps, weight_decay
         self.grad_norm, self.warmup_steps, self.group, self.bucket_bytes = grad_norm, warmup_steps, group, bucket_bytes
         self.overlap = overlap
@@ -454,7 +483,7 @@ class FastSpeech2Trainer:
 
     @torch.no_grad()
     def eval_step(self, batch):
-        with precision_convs(self.precision):
+        with precision_convs(self.precision), emul_attention(self.attention == "fp32_bf16x3"):
             return self._eval_step(batch)
 
     def _eval_step(self, batch):
@@ -615,7 +644,8 @@ class FastSpeech2Trainer:
         return out
 
     def train_step(self, batch):
-        with precision_convs(self.precision):
+        # (around the whole step: compute_losses and the backward of _train_step and of _graph_step's eager, capturing and replaying forms)
+        with precision_convs(self.precision), emul_attention(self.attention == "fp32_bf16x3"):
             return self._train_step_any(batch)
 
     def _train_step_any(self, batch):
