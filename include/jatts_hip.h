@@ -689,6 +689,22 @@ int jatts_gaussian_upsample(const jatts_ragged* rg_in, const int64_t* d, const i
                             int32_t max_out_len, const float* hs, int32_t dim, float delta,
                             float* out, void* stream);
 
+/* Masked Gaussian upsampling on the padded batch, the training form (modules/length_regulator.py:141-153 under autograd; the MAS trainers'
+ * tpos / cen / energy / masked_fill / softmax / bmm lines): c_j = cumsum(ds)_j - ds_j / 2 (float; ds (B, Tm) f32 MAS durations, no gradient),
+ * frame f < kvo[b] sits at t = f and a padded frame at t = 0, tokens j >= kv[b] get weight 0,
+ *   out[b][f][:] = sum_j softmax_j(-delta (t - c_j)^2) hs[b][j][:]   for ALL To frames.
+ * hs: f32 [B * Tm][C]; kv / kvo: int32 [B] on the device; out: f32 [B * To][C]; stat: f32 [B * To][2] = (row maximum, 1 / denominator), what the
+ * backward recomputes the weights from.  One expf per (frame, token); the product runs on v_mfma_f32_32x32x2_f32 (exact f32).  Tm <= 512, else
+ * JATTS_ERR_UNSUPPORTED.  An utterance with kv[b] <= 0 gets zero rows and stat (-inf, 0) where the torch expression gives NaN (a softmax over no
+ * token); kv[b] is clamped to Tm, kvo[b] is only compared with the frame index (any value is safe: frames at or above it sit at t = 0). */
+int jatts_gaussian_upsample_fwd(const float* hs, const float* ds, const int32_t* kv, const int32_t* kvo, int32_t B, int32_t Tm, int32_t To,
+                                int32_t C, float delta, float* out, float* stat, void* stream);
+/* Its gradient for hs (the bmm backward of length_regulator.py:153): d_hs[b][j][:] = sum_f p[b][f][j] g[b][f][:] over all To frames in increasing
+ * order inside one workgroup (no atomics: bit-identical run to run), p recomputed from ds and stat, exact zeros at tokens j >= kv[b].
+ * g: f32 [B * To][C]; d_hs: f32 [B * Tm][C]. */
+int jatts_gaussian_upsample_bwd(const float* g, const float* ds, const float* stat, const int32_t* kv, const int32_t* kvo, int32_t B, int32_t Tm,
+                                int32_t To, int32_t C, float delta, float* d_hs, void* stream);
+
 /* Stage-4 output: float waveform -> little-endian 16-bit PCM, the conversion libsndfile applies for
  * sf.write(path, y, fs, "PCM_16") (jatts/bin/tts_decode.py:250-255): y[i] = lrintf(clamp(x[i], -1, 1) * 32767.f). */
 int jatts_pcm16(const float* x, int64_t n, int16_t* y, void* stream);
@@ -703,6 +719,17 @@ int jatts_pcm16(const float* x, int64_t n, int16_t* y, void* stream);
  * cu_text: int32 [n_seq + 1] token offsets, log_p: f32 [frame rows][ld], ld >= max_text_len <= 512. */
 int jatts_alignment_logp(const jatts_ragged* rg_feats, const int32_t* cu_text, int32_t max_text_len, const float* feats,
                          const float* text, int32_t adim, float* log_p, int32_t ld, void* stream);
+
+/* Gradient of jatts_alignment_logp (modules/alignments.py:50-60 under autograd), same geometry, all f32, two fixed-order passes without atomics:
+ * g = dlog_p at the utterance's own tokens (0 elsewhere), dscore = g - exp(log_p) sum_j g, the squared distance recomputed by direct differences
+ * (exp(log_p) is re-evaluated from those distances, more accurately summed than the forward's; the saved log_p only marks -inf columns),
+ * w = -dscore / sqrt(max(d^2, 1e-24)) -> the workspace w f32 [frame rows][ld];  d_feats[i] = sum_j w_ij (f_i - t_j) f32 [frame rows][adim];
+ * d_text[j] = sum_i w_ij (t_j - f_i) f32 [token rows][adim] (the valid-packed token rows of cu_text).  log_p: the forward's output, row pitch ld;
+ * dlog_p: row pitch ld_g; both >= max_text_len.  max_text_len <= 492: the token tile (65 floats a token), the frame tile and the 16 x T weights
+ * share the CU's 160 KiB of LDS, (81 T + 1040) x 4 bytes -- the limit jatts_alignment_logp has in practice too; above it JATTS_ERR_UNSUPPORTED. */
+int jatts_alignment_logp_bwd(const jatts_ragged* rg_feats, const int32_t* cu_text, int32_t max_text_len, const float* feats,
+                             const float* text, int32_t adim, const float* log_p, int32_t ld, const float* dlog_p, int32_t ld_g,
+                             float* w, float* d_feats, float* d_text, void* stream);
 
 /* Monotonic alignment search + duration extraction for the whole batch (modules/alignments.py:63-93
  * _monotonic_alignment_search, :281-310 viterbi_decode; the reference runs a numba loop per utterance on the host):

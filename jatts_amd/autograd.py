@@ -436,6 +436,48 @@ class ResidualDropAdd(torch.autograd.Function):
         return (dy if ctx.needs_input_grad[0] else None), dh, None, None, None, None
 
 
+# Routing of the MAS trainers' own kernels (round 11), by the project's rule: a piece is True only if the alternating table of tools/bench_mas_ops.py shows it
+# no slower than the sequence it replaces by more than that sequence's own run-to-run spread.  Measured (profiles/r11_notes.md, B 32 x 128 tokens x 768 frames):
+# upsampling forward + backward 194.1 us against 179.6, alignment backward 611.2 us against 573.1, spread 0.0 - 0.2 % -- both lose, both stay False = the
+# sequence of round 10: torch.softmax + autograd.BMM for the upsampling, the float64 torch.matmul form for the alignment backward.  The kernels,
+# hip.gaussian_upsample_fwd / _bwd, hip.alignment_logp_bwd and GaussianUpsample below are there either way.
+MAS_OWN_KERNELS = {"upsample": False, "align_bwd": False}
+
+
+def masked_gaussian_upsample(hs, ds, kv, kvo, tm_, fm, B, Tm, To, delta=0.1):
+    """Masked Gaussian upsampling of the MAS trainers (length_regulator.py:110-154): hs (B * Tm, C), ds (B, Tm) MAS durations, kv / kvo int32 valid tokens /
+    frames, tm_ (B, Tm) bool / fm (B, To) float the same as masks -> (B, To, C).  Padded frames sit at t = 0; the weights depend on the (integer) durations only."""
+    C_ = hs.shape[1]
+    if MAS_OWN_KERNELS["upsample"]:
+        return GaussianUpsample.apply(hs, ds, kv, kvo, B, Tm, To, delta).view(B, To, C_)
+    tpos = torch.arange(To, device=hs.device).float().unsqueeze(0) * fm
+    cen = ds.cumsum(-1) - ds / 2
+    energy = -delta * (tpos.unsqueeze(-1) - cen.unsqueeze(1)) ** 2
+    p_up = torch.softmax(energy.masked_fill(~tm_.unsqueeze(1), float("-inf")), dim=2)
+    return BMM.apply(p_up.unsqueeze(1), hs.view(B, 1, Tm, C_), False).squeeze(1)      # jatts_bgemm
+
+
+class GaussianUpsample(torch.autograd.Function):
+    """Masked Gaussian upsampling of the MAS trainers (length_regulator.py:111-154 on the padded batch): hs (B * Tm, C), ds (B, Tm) float MAS
+    durations, kv / kvo int32 (B,) valid tokens / frames -> (B * To, C); padded frames sit at t = 0, padded tokens weigh 0.  One launch each way
+    (jatts_gaussian_upsample_fwd / _bwd); the (B, To, Tm) weights never reach memory: the backward recomputes them from ds and the per-frame
+    (maximum, 1 / denominator) the forward keeps.  Gradient for hs only: the weights depend on the integer durations alone."""
+
+    @staticmethod
+    def forward(ctx, hs, ds, kv, kvo, B, Tm, To, delta=0.1):
+        ds = ds.detach().float().contiguous()
+        out, stat = hip.gaussian_upsample_fwd(ds, hs.contiguous(), kv, kvo, B, Tm, To, delta)
+        ctx.save_for_backward(ds, stat, kv, kvo)
+        ctx.geom = (B, Tm, To, delta)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ds, stat, kv, kvo = ctx.saved_tensors
+        B, Tm, To, delta = ctx.geom
+        return hip.gaussian_upsample_bwd(ds, stat, g.contiguous(), kv, kvo, B, Tm, To, delta), None, None, None, None, None, None, None
+
+
 class ForwardSum(torch.autograd.Function):
     """ForwardSumLoss.forward after the prior has been added (losses/forward_sum_loss.py:58-78): mean over the batch of the
     per-utterance CTC losses; the gradient is the one torch's ctc_loss backward produces."""
@@ -455,9 +497,10 @@ class ForwardSum(torch.autograd.Function):
 class AlignLogProb(torch.autograd.Function):
     """AlignmentModule.forward after its convolutions (alignments.py:50-60): log_softmax over the valid text tokens of
     -||feats_i - text_j||_2, -inf at padded tokens.  ff (B*To, A) frame features, tf (B*Tm, A) padded token features.
-    forward: jatts_alignment_logp.  backward: log-softmax backward, then with w = -d_score / dist,
-    d_ff_i = (sum_j w_ij) f_i - sum_j w_ij t_j and d_tf_j = (sum_i w_ij) t_j - sum_i w_ij f_i: two batched GEMMs (rocBLAS) and
-    element-wise ops on the (B, To, Tm) matrices (f64 for the distance recomputed in its GEMM form)."""
+    forward: jatts_alignment_logp.  backward, by MAS_OWN_KERNELS["align_bwd"]: True = jatts_alignment_logp_bwd -- the log-softmax backward, then with
+    w = -d_score / dist (the distance recomputed by direct differences, as the forward kernel does), d_ff_i = sum_j w_ij (f_i - t_j) and
+    d_tf_j = sum_i w_ij (t_j - f_i): f32, two fixed-order passes, no atomics; the token gradient is scattered back to the padded rows (zeros at padded
+    tokens; the kernel masks by `ilens`, which is what `valid` is built from).  False = the round-10 form, float64 torch ops and three torch.matmul calls."""
 
     @staticmethod
     def forward(ctx, ff, tf, B, ilens, tsel=None, valid=None):
@@ -476,14 +519,25 @@ class AlignLogProb(torch.autograd.Function):
         n = min(Tm, lp3.shape[2])
         lp[:, :, :n] = lp3[:, :, :n]
         lp = lp.masked_fill(~valid.unsqueeze(1), float("-inf"))
-        ctx.save_for_backward(ff, tf, lp, valid)
-        ctx.B = B
+        ctx.save_for_backward(ff, tf, lp, tsel, valid)
+        ctx.B, ctx.ilens = B, [int(v) for v in ilens]
         return lp
 
     @staticmethod
     def backward(ctx, dlp):
-        ff, tf, lp, valid = ctx.saved_tensors
+        ff, tf, lp, tsel, valid = ctx.saved_tensors
         B = ctx.B
+        To = ff.shape[0] // B
+        if not MAS_OWN_KERNELS["align_bwd"]:
+            return AlignLogProb._backward_f64(ff, tf, lp, valid, dlp, B) + (None, None, None, None)
+        rbf, rbv = hip.RaggedBatch([To] * B, ff.device), hip.RaggedBatch(ctx.ilens, ff.device)
+        dF, dTv = hip.alignment_logp_bwd(rbf, rbv, ff.contiguous(), tf.index_select(0, tsel).contiguous(), lp, dlp.contiguous().float())
+        dT = torch.zeros_like(tf).index_copy(0, tsel, dTv)
+        return dF, dT, None, None, None, None
+
+    @staticmethod
+    def _backward_f64(ff, tf, lp, valid, dlp, B):
+        """The round-10 form (MAS_OWN_KERNELS["align_bwd"] False): float64 element-wise ops and three torch.matmul calls (rocBLAS), the distance in its GEMM form."""
         To, Tm, A_ = ff.shape[0] // B, tf.shape[0] // B, ff.shape[1]
         vm = valid.unsqueeze(1)
         g = dlp.double().masked_fill(~vm, 0.0)
@@ -496,7 +550,7 @@ class AlignLogProb(torch.autograd.Function):
         # memset, which did not replay reliably inside a captured step on this stack (garbage text-side gradients at B 32 x 768 frames)
         wF = torch.matmul(w.transpose(1, 2), torch.cat([F_, torch.ones(B, To, 1, dtype=F_.dtype, device=F_.device)], dim=-1))
         dT = wF[..., A_:] * T_ - wF[..., :A_]
-        return dF.reshape(B * To, A_).float(), dT.reshape(B * Tm, A_).float(), None, None, None, None
+        return dF.reshape(B * To, A_).float(), dT.reshape(B * Tm, A_).float()
 
 
 class WeightNorm(torch.autograd.Function):

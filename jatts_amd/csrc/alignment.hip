@@ -175,6 +175,194 @@ __global__ __launch_bounds__(256) void align_logp_kernel(jatts_ragged rg_f, cons
   }
 }
 
+// Gradient of align_logp_kernel, all f32, two fixed-order passes (no atomics, no split reductions: two runs are bit-identical).
+// Pass 1, one workgroup per 16 frames (the forward's tiling): the squared distance again by DIRECT differences (no |f|^2 + |t|^2 - 2 f.t
+// cancellation, which is what the float64 form of this gradient was for), g = dlog_p at the utterance's own tokens, dscore = g - exp(log_p) sum_j g
+// with exp(log_p) RE-EVALUATED as softmax_j(-dist) from the distances of this kernel: the saved log_p carries the forward's single-chain sum over the
+// channels (1.7e-5 absolute at 384 channels), a factor common to a frame's probabilities that sum_j g multiplies -- measured 5.2 x the f32 CPU
+// evaluation's error in d_feats at (2, 260, 130, 384) when read back, profiles/r11_notes.md; log_p only tells which columns the caller masked,
+// w = -dscore / sqrt(max(d^2, 1e-24)) -> the workspace, and d_feats_i = sum_j w_ij (f_i - t_j), tokens in increasing order.
+// The contractions are plain FMAs from LDS, not MFMAs: the operand of each product is a DIFFERENCE (f_ic - t_jc), which the matrix pipe could only take
+// in the expanded form (sum_j w_ij) f_i - sum_j w_ij t_j with its cancellation, and one LDS read feeds four subtract + FMA pairs here.
+constexpr int ALB_TT = 32;   // pass 2: tokens per workgroup
+constexpr int ALB_FK = 32;   //         frames per staged chunk
+
+__global__ __launch_bounds__(256) void align_logp_bwd_frames_kernel(jatts_ragged rg_f, const int32_t* cu_text, const float* __restrict__ feats,
+                                                                    const float* __restrict__ text, int adim, const float* __restrict__ logp, int ld,
+                                                                    const float* __restrict__ dlogp, int ldg, float* __restrict__ wout,
+                                                                    float* __restrict__ d_feats) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int b = blockIdx.y;
+  const int row0 = rg_f.cu_rows[b];
+  const int T_f = rg_f.cu_rows[b + 1] - row0;
+  const int f0 = blockIdx.x * AL_FB;
+  if (f0 >= T_f) return;
+  const int tok0 = cu_text[b];
+  const int T_t = cu_text[b + 1] - tok0;
+  const int nf = min(AL_FB, T_f - f0);
+  float* sc = reinterpret_cast<float*>(smem);            // [T_t][AL_FB]: d^2, then w (16-byte rows: one broadcast ds_read_b128 per four frames)
+  float* fs = sc + (size_t)max(T_t, 0) * AL_FB;          // [AL_FB][AL_CC + 1]
+  float* ts = fs + AL_FB * (AL_CC + 1);                  // [T_t][AL_CC + 1]
+  const int pairs = nf * T_t;
+  float acc[AL_PAIRS];
+#pragma unroll
+  for (int p = 0; p < AL_PAIRS; ++p) acc[p] = 0.f;
+  for (int c0 = 0; c0 < adim; c0 += AL_CC) {
+    const int cc = min(AL_CC, adim - c0);
+    __syncthreads();
+    for (int u = threadIdx.x; u < T_t * cc; u += 256) {
+      const int i = u / cc, c = u - i * cc;
+      ts[i * (AL_CC + 1) + c] = text[(int64_t)(tok0 + i) * adim + c0 + c];
+    }
+    for (int u = threadIdx.x; u < nf * cc; u += 256) {
+      const int f = u / cc, c = u - f * cc;
+      fs[f * (AL_CC + 1) + c] = feats[(int64_t)(row0 + f0 + f) * adim + c0 + c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < AL_PAIRS; ++p) {
+      const int u = threadIdx.x + 256 * p;
+      if (u < pairs) {
+        const int f = u / T_t, i = u - f * T_t;
+        const float* tr = ts + i * (AL_CC + 1);
+        const float* fr = fs + f * (AL_CC + 1);
+        // four partial sums per chunk, joined pairwise, then one add into the running total: a single chain over 384 channels carries ~10 ulp of
+        // d^2 into the distance, which the softmax below turns into a common factor of a frame's probabilities (see the kernel's head)
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        int c = 0;
+        for (; c + 4 <= cc; c += 4) {
+          const float d0 = fr[c] - tr[c], d1 = fr[c + 1] - tr[c + 1], d2 = fr[c + 2] - tr[c + 2], d3 = fr[c + 3] - tr[c + 3];
+          a0 += d0 * d0; a1 += d1 * d1; a2 += d2 * d2; a3 += d3 * d3;
+        }
+        for (; c < cc; ++c) { const float dlt = fr[c] - tr[c]; a0 += dlt * dlt; }
+        acc[p] += (a0 + a1) + (a2 + a3);
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < AL_PAIRS; ++p) {
+    const int u = threadIdx.x + 256 * p;
+    if (u < pairs) { const int f = u / T_t, i = u - f * T_t; sc[i * AL_FB + f] = acc[p]; }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int f = wave; f < AL_FB; f += 4) {
+    if (f >= nf) {                                       // (uniform per wave) frames past the utterance: zero weights, nothing written
+      for (int i = lane; i < T_t; i += 64) sc[i * AL_FB + f] = 0.f;
+      continue;
+    }
+    const float* gr = dlogp + (int64_t)(row0 + f0 + f) * ldg;
+    const float* lr = logp + (int64_t)(row0 + f0 + f) * ld;
+    float gs = 0.f, mx = -INFINITY;
+    // (a column whose saved log_p is -inf was masked by the caller: it is left out of the softmax as it was in the forward, its probability is 0)
+    for (int i = lane; i < T_t; i += 64) { gs += gr[i]; if (isfinite(lr[i])) mx = fmaxf(mx, -sqrtf(sc[i * AL_FB + f])); }
+    gs = wave_sum(gs);
+    mx = wave_max(mx);
+    float se = 0.f;
+    for (int i = lane; i < T_t; i += 64) se += isfinite(lr[i]) ? expf(-sqrtf(sc[i * AL_FB + f]) - mx) : 0.f;
+    const float lse = mx + logf(wave_sum(se));
+    float* wr = wout + (int64_t)(row0 + f0 + f) * ld;
+    for (int i = lane; i < ld; i += 64) {
+      float w = 0.f;
+      if (i < T_t) {
+        const float d2 = sc[i * AL_FB + f];
+        const float prob = isfinite(lr[i]) ? expf(-sqrtf(d2) - lse) : 0.f;      // (a column the caller masked to -inf stays at probability 0)
+        const float dscore = gr[i] - prob * gs;
+        w = -dscore / sqrtf(fmaxf(d2, 1e-24f));
+        sc[i * AL_FB + f] = w;
+      }
+      wr[i] = w;
+    }
+  }
+  // d_feats: thread = (channel c of the staged chunk, four frames); tokens in increasing order
+  const int c = threadIdx.x & 63, fg = threadIdx.x >> 6;
+  for (int c0 = 0; c0 < adim; c0 += AL_CC) {
+    const int cc = min(AL_CC, adim - c0);
+    __syncthreads();
+    for (int u = threadIdx.x; u < T_t * cc; u += 256) {
+      const int i = u / cc, k = u - i * cc;
+      ts[i * (AL_CC + 1) + k] = text[(int64_t)(tok0 + i) * adim + c0 + k];
+    }
+    float fv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int f = min(4 * fg + k, nf - 1), ck = min(c, cc - 1);
+      fv[k] = feats[(int64_t)(row0 + f0 + f) * adim + c0 + ck];
+    }
+    __syncthreads();
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < T_t; ++i) {
+      const float tv = ts[i * (AL_CC + 1) + c];
+      const f32x4 w4 = *reinterpret_cast<const f32x4*>(sc + i * AL_FB + 4 * fg);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] += w4[k] * (fv[k] - tv);
+    }
+    if (c < cc) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (4 * fg + k < nf) d_feats[(int64_t)(row0 + f0 + 4 * fg + k) * adim + c0 + c] = a[k];
+    }
+  }
+}
+
+// Pass 2, one workgroup per (32 tokens, 64 channels) of one utterance: d_text_j = sum_i w_ij (t_j - f_i), the frames walked in increasing order through a
+// double-buffered LDS chunk of 32 frames (features and weights); thread = (channel, eight tokens).
+__global__ __launch_bounds__(256) void align_logp_bwd_tokens_kernel(jatts_ragged rg_f, const int32_t* cu_text, const float* __restrict__ feats,
+                                                                    const float* __restrict__ text, int adim, const float* __restrict__ w, int ld,
+                                                                    float* __restrict__ d_text) {
+  __shared__ __attribute__((aligned(16))) float fs[2][ALB_FK * (AL_CC + 1)];
+  __shared__ __attribute__((aligned(16))) float ws[2][ALB_FK * ALB_TT];
+  const int b = blockIdx.z;
+  const int row0 = rg_f.cu_rows[b];
+  const int T_f = rg_f.cu_rows[b + 1] - row0;
+  const int tok0 = cu_text[b];
+  const int T_t = cu_text[b + 1] - tok0;
+  const int j0 = blockIdx.x * ALB_TT, c0 = blockIdx.y * AL_CC;
+  if (j0 >= T_t) return;
+  const int cc = min(AL_CC, adim - c0);
+  const int c = threadIdx.x & 63, tg = threadIdx.x >> 6;      // tokens j0 + 8 tg + k
+  const int ck = min(c, cc - 1);
+  float tv[8], a[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int j = min(j0 + 8 * tg + k, T_t - 1);
+    tv[k] = text[(int64_t)(tok0 + j) * adim + c0 + ck];
+    a[k] = 0.f;
+  }
+  for (int f0 = 0; f0 < T_f; f0 += ALB_FK) {
+    const int buf = (f0 / ALB_FK) & 1;
+    for (int u = threadIdx.x; u < ALB_FK * AL_CC; u += 256) {
+      const int i = u >> 6, k = u & 63;
+      const bool ok = f0 + i < T_f && k < cc;
+      const float v = feats[(int64_t)(row0 + min(f0 + i, T_f - 1)) * adim + c0 + min(k, cc - 1)];
+      fs[buf][i * (AL_CC + 1) + k] = ok ? v : 0.f;
+    }
+    for (int u = threadIdx.x; u < ALB_FK * ALB_TT; u += 256) {
+      const int i = u >> 5, k = u & 31;
+      const bool ok = f0 + i < T_f && j0 + k < T_t;
+      const float v = w[(int64_t)(row0 + min(f0 + i, T_f - 1)) * ld + min(j0 + k, T_t - 1)];
+      ws[buf][i * ALB_TT + k] = ok ? v : 0.f;
+    }
+    __syncthreads();      // (the buffer written two chunks on was last read before the barrier of the chunk in between)
+#pragma unroll 4
+    for (int i = 0; i < ALB_FK; ++i) {
+      const float fv = fs[buf][i * (AL_CC + 1) + c];
+      const f32x4 w0 = *reinterpret_cast<const f32x4*>(&ws[buf][i * ALB_TT + 8 * tg]);
+      const f32x4 w1 = *reinterpret_cast<const f32x4*>(&ws[buf][i * ALB_TT + 8 * tg + 4]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        a[k] += w0[k] * (tv[k] - fv);
+        a[4 + k] += w1[k] * (tv[4 + k] - fv);
+      }
+    }
+  }
+  if (c < cc) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (j0 + 8 * tg + k < T_t) d_text[(int64_t)(tok0 + j0 + 8 * tg + k) * adim + c0 + c] = a[k];
+  }
+}
+
 }  // namespace
 
 extern "C" int jatts_mas_viterbi(const jatts_ragged* rg_feats, const int32_t* cu_text, const float* log_p, int32_t ld,
@@ -203,6 +391,30 @@ extern "C" int jatts_alignment_logp(const jatts_ragged* rg_feats, const int32_t*
   JATTS_RAISE_LDS_LIMIT(align_logp_kernel);
   dim3 grid((unsigned)((rg_feats->max_len + AL_FB - 1) / AL_FB), (unsigned)rg_feats->n_seq);
   hipLaunchKernelGGL(align_logp_kernel, grid, dim3(256), lds, (hipStream_t)stream, *rg_feats, cu_text, feats, text, adim, log_p, ld);
+  JATTS_CHECK_LAUNCH();
+  return JATTS_OK;
+}
+
+extern "C" int jatts_alignment_logp_bwd(const jatts_ragged* rg_feats, const int32_t* cu_text, int32_t max_text_len, const float* feats,
+                                        const float* text, int32_t adim, const float* log_p, int32_t ld, const float* dlog_p, int32_t ld_g,
+                                        float* w, float* d_feats, float* d_text, void* stream) {
+  if (!rg_feats || !rg_feats->cu_rows || !cu_text || !feats || !text || !log_p || !dlog_p || !w || !d_feats || !d_text)
+    return jatts_set_error_msg(JATTS_ERR_ARG, "alignment_logp_bwd: null pointer");
+  if (max_text_len < 1 || AL_FB * max_text_len > 256 * AL_PAIRS || ld < max_text_len || ld_g < max_text_len)
+    return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "alignment_logp_bwd: text length must be 1..512 and <= ld, ld_g");
+  if (adim < 1 || rg_feats->n_seq > 65535) return jatts_set_error_msg(JATTS_ERR_ARG, "alignment_logp_bwd: bad size");
+  if (rg_feats->n_seq < 1) return JATTS_OK;
+  const size_t lds = ((size_t)max_text_len * (AL_CC + 1) + (size_t)AL_FB * (AL_CC + 1) + (size_t)AL_FB * max_text_len) * sizeof(float);
+  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "alignment_logp_bwd: text too long for LDS (max_text_len <= 492, as jatts_alignment_logp)");
+  if (rg_feats->max_len > 0) {
+    JATTS_RAISE_LDS_LIMIT(align_logp_bwd_frames_kernel);
+    dim3 grid((unsigned)((rg_feats->max_len + AL_FB - 1) / AL_FB), (unsigned)rg_feats->n_seq);
+    hipLaunchKernelGGL(align_logp_bwd_frames_kernel, grid, dim3(256), lds, (hipStream_t)stream, *rg_feats, cu_text, feats, text, adim, log_p, ld, dlog_p,
+                       ld_g, w, d_feats);
+    JATTS_CHECK_LAUNCH();
+  }
+  dim3 grid2((unsigned)((max_text_len + ALB_TT - 1) / ALB_TT), (unsigned)((adim + AL_CC - 1) / AL_CC), (unsigned)rg_feats->n_seq);
+  hipLaunchKernelGGL(align_logp_bwd_tokens_kernel, grid2, dim3(256), 0, (hipStream_t)stream, *rg_feats, cu_text, feats, text, adim, w, ld, d_text);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }

@@ -1126,6 +1126,63 @@ def alignment_logp(rb_f, rb_t, feats, text, adim):
     return out
 
 
+def alignment_logp_bwd(rb_f, rb_t, feats, text, log_p, dlog_p):
+    """jatts_alignment_logp_bwd: the gradient of alignment_logp in f32, two fixed-order passes.  feats (frame rows, A), text (valid-packed token rows,
+    A), log_p / dlog_p (frame rows, >= max text length) f32 -> (d_feats (frame rows, A), d_text (token rows, A))."""
+    lib = _abi.load()
+    for v in (feats, text, log_p, dlog_p):
+        if _dev(v).dtype != torch.float32 or not v.is_contiguous():
+            raise ValueError("alignment_logp_bwd: contiguous float32 tensors expected")
+    adim = feats.shape[1]
+    lp2, dl2 = log_p.reshape(rb_f.total, -1), dlog_p.reshape(rb_f.total, -1)
+    if feats.shape[0] != rb_f.total or text.shape != (rb_t.total, adim):
+        raise ValueError("alignment_logp_bwd: feats / text do not match the batch geometry")
+    w = torch.empty_like(lp2)
+    d_feats = torch.empty_like(feats)
+    d_text = torch.empty_like(text)
+    rg = rb_f.struct()
+    _abi.check(lib.jatts_alignment_logp_bwd(C.byref(rg), rb_t.cu.data_ptr(), rb_t.max_len, feats.data_ptr(), text.data_ptr(), adim, lp2.data_ptr(),
+                                            lp2.shape[1], dl2.data_ptr(), dl2.shape[1], w.data_ptr(), d_feats.data_ptr(), d_text.data_ptr(),
+                                            _stream()), "jatts_alignment_logp_bwd")
+    return d_feats, d_text
+
+
+def _gauss_args(what, ds, x, kv, kvo, B, Tm, To, rows):
+    if _dev(x).dtype != torch.float32 or not x.is_contiguous() or x.dim() != 2 or x.shape[0] != B * rows:
+        raise ValueError(f"{what}: contiguous float32 (B * {rows}, C) expected")
+    if _dev(ds).dtype != torch.float32 or not ds.is_contiguous() or ds.numel() != B * Tm:
+        raise ValueError(f"{what}: ds must be contiguous float32 (B, Tm)")
+    for v in (kv, kvo):
+        if _dev(v).dtype != torch.int32 or not v.is_contiguous() or v.numel() != B:
+            raise ValueError(f"{what}: kv / kvo must be int32 (B,) device tensors")
+
+
+def gaussian_upsample_fwd(ds, hs, kv, kvo, B, Tm, To, delta=0.1):
+    """jatts_gaussian_upsample_fwd: masked Gaussian upsampling on the padded batch.  ds (B, Tm) f32 durations, hs (B * Tm, C) f32, kv / kvo int32 (B,)
+    valid tokens / frames -> (out (B * To, C), stat (B * To, 2) = row maximum and 1 / denominator for the backward)."""
+    lib = _abi.load()
+    _gauss_args("gaussian_upsample_fwd", ds, hs, kv, kvo, B, Tm, To, Tm)
+    Cc = hs.shape[1]
+    out = torch.empty(B * To, Cc, dtype=torch.float32, device=hs.device)
+    stat = torch.empty(B * To, 2, dtype=torch.float32, device=hs.device)
+    _abi.check(lib.jatts_gaussian_upsample_fwd(hs.data_ptr(), ds.data_ptr(), kv.data_ptr(), kvo.data_ptr(), B, Tm, To, Cc, float(delta),
+                                               out.data_ptr(), stat.data_ptr(), _stream()), "jatts_gaussian_upsample_fwd")
+    return out, stat
+
+
+def gaussian_upsample_bwd(ds, stat, g, kv, kvo, B, Tm, To, delta=0.1):
+    """jatts_gaussian_upsample_bwd: g (B * To, C) f32 -> d_hs (B * Tm, C), exact zeros at padded tokens; the weights are recomputed from ds and stat."""
+    lib = _abi.load()
+    _gauss_args("gaussian_upsample_bwd", ds, g, kv, kvo, B, Tm, To, To)
+    if _dev(stat).dtype != torch.float32 or not stat.is_contiguous() or stat.numel() != 2 * B * To:
+        raise ValueError("gaussian_upsample_bwd: stat must be the forward's (B * To, 2) float32 tensor")
+    Cc = g.shape[1]
+    d_hs = torch.empty(B * Tm, Cc, dtype=torch.float32, device=g.device)
+    _abi.check(lib.jatts_gaussian_upsample_bwd(g.data_ptr(), ds.data_ptr(), stat.data_ptr(), kv.data_ptr(), kvo.data_ptr(), B, Tm, To, Cc,
+                                               float(delta), d_hs.data_ptr(), _stream()), "jatts_gaussian_upsample_bwd")
+    return d_hs
+
+
 def mas_viterbi(rb_f, rb_t, log_p):
     """jatts_mas_viterbi -> (path int64 (frame rows,), dur int64 (token rows,), score f64 (n_seq,))."""
     lib = _abi.load()

@@ -169,11 +169,7 @@ def train_forward(model, text, text_lengths, feats, feats_lengths, durations, du
         picked = torch.gather(log_p_attn, 2, path.unsqueeze(-1)).squeeze(-1).masked_fill(fm == 0, 0.0)
         bin_loss = -(picked.sum(1) / kvo.float()).mean()                                   # alignments.py:307-309
         # masked Gaussian upsampling (length_regulator.py:110-154): the weights depend on the (integer) durations only
-        tpos = torch.arange(To, device=dev).float().unsqueeze(0) * fm                       # padded frames sit at t = 0
-        cen = ds.cumsum(-1) - ds / 2
-        energy = -0.1 * (tpos.unsqueeze(-1) - cen.unsqueeze(1)) ** 2
-        p_up = torch.softmax(energy.masked_fill(~tm_.unsqueeze(1), float("-inf")), dim=2)
-        up = A.BMM.apply(p_up.unsqueeze(1), hs.view(B, 1, Tm, Ad), False).squeeze(1)[:, :Te].reshape(B * Te, Ad)   # jatts_bgemm
+        up = A.masked_gaussian_upsample(hs, ds, kv, kvo, tm_, fm, B, Tm, To)[:, :Te].reshape(B * Te, Ad)
         extra.update(bin_loss=bin_loss, log_p_attn=log_p_attn, ds=ds)
     else:
         d_flat = durations[:, : int(durations_lengths.max())].to(dev).reshape(-1).to(torch.int64).contiguous()

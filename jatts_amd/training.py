@@ -93,7 +93,7 @@ def emul_convs(on=True):
         EMUL_CONVS[0] = prev
 
 
-# attention="fp32_bf16x3" of the trainers (round 10): the attention products of autograd.BMM -- q k^T, q p^T, P v, the Gaussian-upsampling p_up @ hs and their
+# attention="fp32_bf16x3" of the trainers (round 10): the attention products of autograd.BMM -- q k^T, q p^T, P v, the Gaussian-upsampling p_up @ hs (while autograd.MAS_OWN_KERNELS leaves it on BMM) and their
 # gradients -- on the same emulated arithmetic (jatts_bgemm_emul) where emul_bgemm_wins routes them.  A switch of its own, independent of the conv modes.
 EMUL_ATTENTION = [False]
 TRAIN_ATTENTIONS = {
