@@ -124,7 +124,9 @@ typedef struct jatts_conv_desc {
   int32_t n_out;       /* true output channels (packed rows = round_up(n_out, 32)) */
   int32_t k_w;         /* taps */
   int32_t dil;
-  int32_t pad;         /* input offset: tap 0 reads row t - pad */
+  int32_t pad;         /* input offset: tap 0 reads row t - pad.  0 <= pad <= (k_w - 1) * dil (left halo pad, right halo (k_w - 1) * dil - pad; asymmetric
+                        * and one-sided halos are fine, e.g. k_w = 2, pad = 1 or k_w = 4, pad = 2); anything else is JATTS_ERR_ARG: a tap would
+                        * read only padding, and the 32-bit row offsets of the register-streamed f32 kernel are proven for this range only */
   const float* bias;   /* [n_out] or NULL */
   int32_t act;         /* JATTS_ACT_* */
   float alpha;
@@ -267,6 +269,7 @@ int jatts_masked_loss(const jatts_ragged* rg, const float* a, int32_t lda, const
                       const int32_t* valid_len, int32_t kind, float log_offset, double scale, float* out, double* workspace,
                       void* stream);
 /* dw[n][c][tap] = sum_t dy[t][n] * x[t + tap*dil - pad][c] over all sequences (torch weight layout (n_out, c_in, k_w), f32).
+ * 0 <= pad <= (k_w - 1) * dil as for jatts_conv1d (JATTS_ERR_ARG otherwise; jatts_conv1d_wgrad_emul alike); rg->len_mul scales every sequence as there.
  * workspace != NULL (n_seq * (k_w * pad64(n_out) * pad64(c_in) + pad64(n_out)) floats): split-K partials are written there and summed
  * by a second launch, dw is OVERWRITTEN (deterministic, no atomics).  workspace == NULL: refused on the MFMA path (k_w 1 / 3 / 5); the VALU
  * path (other widths) then ACCUMULATES into dw, through the fixed-order slabs of jatts_set_workspace (round 4: no f32 atomics anywhere).

@@ -47,6 +47,10 @@ extern "C" int jatts_conv1d(const jatts_conv_desc* d, void* stream) {
   if (d->ldx % 8) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d: ldx must be a multiple of 8");
   if (d->n_in < 1 || d->n_in > 3 || d->k_w < 1 || d->dil < 1 || d->n_out < 1 || d->rg.n_seq < 1 || d->rg.len_mul < 1)
     return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d: bad geometry");
+  // every tap of every output row reads inside [t - (k_w - 1) dil, t + (k_w - 1) dil]: the range the register-streamed kernel's 32-bit row offsets
+  // are proven for (conv1d_direct.h: conv_direct_ok) and every caller stays in (a "same" conv, its data gradient, the polyphase forms)
+  if (d->pad < 0 || (int64_t)d->pad > (int64_t)(d->k_w - 1) * d->dil)
+    return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d: pad must lie in [0, (k_w - 1) * dil]");
   if (d->act == JATTS_ACT_SNAKEBETA && (!d->act_a || !d->act_b || (d->n_out & 3) || ((uintptr_t)d->act_a & 15) || ((uintptr_t)d->act_b & 15)))
     return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d: JATTS_ACT_SNAKEBETA needs 16-byte aligned act_a / act_b and n_out % 4 == 0");
   if (d->n_split != 0 && (d->n_split < 0 || d->n_split % 256 || d->n_split >= d->n_out || !d->y2 || d->y_transposed || d->resid || d->ldy2 <= 0))

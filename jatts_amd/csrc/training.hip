@@ -656,6 +656,7 @@ extern "C" int jatts_conv1d_wgrad(const jatts_ragged* rg, const float* x, int32_
                                   int32_t n_out, int32_t k_w, int32_t dil, int32_t pad, float* dw, float* db, float* workspace, void* stream) {
   if (!rg || !x || !dy || !dw) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad: null pointer");
   if (c_in < 1 || n_out < 1 || k_w < 1 || dil < 1) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad: bad geometry");
+  if (pad < 0 || (int64_t)pad > (int64_t)(k_w - 1) * dil) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad: pad must lie in [0, (k_w - 1) * dil]");
   if (rg->n_seq <= 0 || rg->max_len <= 0) return JATTS_OK;
   const int tiles = ((n_out + 63) / 64) * ((c_in + 63) / 64) * k_w;
   int groups = (1024 + tiles - 1) / tiles;            // enough workgroups to fill the chip; each group strides over the sequences
@@ -702,6 +703,7 @@ extern "C" int jatts_conv1d_wgrad_emul(const jatts_ragged* rg, const float* x, i
   if (dtype != JATTS_F32E) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: dtype must be JATTS_F32E");
   if (!rg || !x || !dy || !dw) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: null pointer");
   if (c_in < 1 || n_out < 1 || k_w < 1 || dil < 1) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: bad geometry");
+  if (pad < 0 || (int64_t)pad > (int64_t)(k_w - 1) * dil) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: pad must lie in [0, (k_w - 1) * dil]");
   // outside the emulated kernel's taps / halo: the exact-f32 entry (the more accurate of the two)
   if (!(k_w == 1 || k_w == 3 || k_w == 5) || (k_w - 1) * dil > WE_HALO) return jatts_conv1d_wgrad(rg, x, ldx, dy, ldy, c_in, n_out, k_w, dil, pad, dw, db, workspace, stream);
   if (rg->n_seq <= 0 || rg->max_len <= 0) return JATTS_OK;

@@ -612,7 +612,8 @@ def conv1d(rb, xs, w_packed, c_in, n_out, k_w, *, dtype, dil=1, pad=None, bias=N
     from pack_conv_weight_split (c_mult 64).  ``snake`` = (exp(alpha), 1 / (exp(beta) + 1e-9)) f32 vectors of n_out: the SnakeBeta
     activation (the ``snakebeta`` op) applied in the epilogue instead of ``act``.  ``split`` = (n_split, ld2, seq_col0): TWO outputs from one launch
     (the Q | K | V projection): channels < n_split row-major as usual, channels >= n_split transposed into a (n_out - n_split, ld2) matrix with the V^T
-    column layout ``seq_col0`` (RaggedBatch.vt_layout); returns (out, out2)."""
+    column layout ``seq_col0`` (RaggedBatch.vt_layout); returns (out, out2).  ``pad`` (default: the "same" offset (k_w - 1) // 2 * dil) must lie in
+    [0, (k_w - 1) * dil]; the library refuses anything else."""
     lib = _abi.load()
     if isinstance(xs, torch.Tensor):
         xs = [xs]
@@ -1287,7 +1288,7 @@ def masked_loss(rb, a, b, valid_len, kind, scale, log_offset=-1.0):
 def conv1d_wgrad(rb, x, dy, c_in, n_out, k_w, dil, pad, len_mul=1, want_db=False, dtype=F32):
     """-> dw (n_out, c_in, k_w); with want_db -> (dw, db): the bias gradient comes out of the same launch (the kernel's dy tiles).
     dtype F32: the exact-f32 kernel; F32E: the emulated weight gradient (jatts_conv1d_wgrad_emul: k_w 1 / 3 / 5, halo <= 32 rows; any other geometry
-    takes the exact-f32 kernel inside the entry point)."""
+    takes the exact-f32 kernel inside the entry point).  ``pad`` must lie in [0, (k_w - 1) * dil], as for conv1d; both entry points refuse anything else."""
     lib = _abi.load()
     if dtype not in (F32, F32E):
         raise ValueError("conv1d_wgrad: dtype F32 (exact) or F32E (three bf16 terms per operand, seven products)")
