@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define JATTS_ABI_VERSION 7   /* (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
+#define JATTS_ABI_VERSION 7   /* (round 13: jatts_hifigan_resunit / jatts_resunit_variant take w2 == NULL as the single-conv dilation unit, without a bump: no descriptor or signature changed, and a library from before it lacks jatts_resunit_single_conv, so it is refused when _abi.load binds that symbol) (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
                                 * so every descriptor that embeds it (jatts_conv_desc, jatts_resunit_desc, jatts_resblock_desc, jatts_relattn_desc) shifted by 8 bytes; JATTS_F32E; 2 (round 4): jatts_conv_desc + w_inv / act_a / act_b, jatts_resunit_desc + ws1 / ws2, jatts_resblock_desc + ws1 / ws2;
                                 * bumped whenever a descriptor's layout or an entry point's signature changes: a stale library is refused at load */
 
@@ -178,6 +178,15 @@ int64_t jatts_conv_weight_index(int32_t n, int32_t tap, int32_t c, int32_t n_pad
  * jatts/vocoder/vocoder.py:64].  x, y: [rows][channels]; w1/w2 packed as above with
  * c_in = n_out = channels.  y must not alias x.  channels in {32, 64, 128, 256, 512}
  * (f32 mode: up to 256); other widths go through two jatts_conv1d launches.
+ *
+ * (round 13) w2 == NULL: the SINGLE-CONV unit of ResBlocks built with use_additional_convs=False (HiFi-GAN V3),
+ *   y = x + conv_k,d( lrelu(x) ) + b1
+ * -- the unit above without lrelu -> conv_k,1 -> + b2; b2 and ws2 must then be NULL too (JATTS_ERR_ARG otherwise).  Same geometry (packed ragged
+ * rows with len_mul, zero outside the utterance, 1-D grid with host_lens), same MRF mix, y must not alias x.  dtype JATTS_F32 (channels 32 .. 256),
+ * JATTS_F16 (32 .. 512), JATTS_F32E / JATTS_F32E6 with w_layout = 1 (32 .. 256); JATTS_F32S and the w_layout = 0 emulated form return
+ * JATTS_ERR_UNSUPPORTED.  Windowed only (there is no inner activation whose halo could be carried): `variant` is ignored and jatts_resunit_variant
+ * reports 1.  A window is channels x (columns + (k_w - 1) dil) in LDS; a shape whose window exceeds 160 KiB is refused before the launch (every
+ * k 3 / 7 / 11 x dilation 1 / 3 / 5 shape launches at every width; (k - 1) dil up to 72 at channels <= 128).  csrc/resunit1_*.
  * ------------------------------------------------------------------------------- */
 typedef struct jatts_resunit_desc {
   jatts_ragged rg;
@@ -190,7 +199,7 @@ typedef struct jatts_resunit_desc {
   void* y;
   const void* w1;
   const float* b1;
-  const void* w2;
+  const void* w2;      /* NULL: the single-conv unit (round 13); b2 and ws2 NULL too */
   const float* b2;
   /* optional MRF mix fused into the (coalesced) output pass: y = out_scale * (unit(x) + add0 + add1);
    * used by the last unit of the last ResBlock so that the mean over ResBlocks
@@ -217,6 +226,10 @@ int jatts_hifigan_resunit(const jatts_resunit_desc* d, void* stream);
 /* The form jatts_hifigan_resunit would launch for d on the current device: 1 = windowed, 2 = sliding (jatts_resunit_desc.variant), or a negative
  * error code.  Launches nothing. */
 int jatts_resunit_variant(const jatts_resunit_desc* d);
+
+/* 1 if jatts_hifigan_resunit has a single-conv kernel (w2 == NULL) for this dtype code and w_layout, else 0: JATTS_F32, JATTS_F16 (w_layout 0) and
+ * JATTS_F32E / JATTS_F32E6 with w_layout 1.  Pure function.  Its presence also marks a library that knows the form at all. */
+int jatts_resunit_single_conv(int32_t dtype, int32_t w_layout);
 
 /* Index of W[n][tap][c] (one of the three bf16 planes' 8-element groups counted as one element) inside a w_layout = 1 buffer (HOST helper, pure function). */
 int64_t jatts_unit_weight_index_k32(int32_t n, int32_t tap, int32_t c, int32_t channels);

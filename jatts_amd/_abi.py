@@ -74,6 +74,7 @@ PROTOTYPES = {
     "jatts_conv_weight_index": (C.c_int64, [C.c_int32] * 5),
     "jatts_hifigan_resunit": (C.c_int, [C.POINTER(ResUnitDesc), C.c_void_p]),
     "jatts_resunit_variant": (C.c_int, [C.POINTER(ResUnitDesc)]),
+    "jatts_resunit_single_conv": (C.c_int, [C.c_int32, C.c_int32]),
     "jatts_unit_weight_index_k32": (C.c_int64, [C.c_int32] * 4),
     "jatts_hifigan_resblock": (C.c_int, [C.POINTER(ResBlockDesc), C.c_void_p]),
     "jatts_debug_trace": (C.c_int, [C.c_void_p, C.c_int64]),

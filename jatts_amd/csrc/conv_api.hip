@@ -16,6 +16,9 @@ int jatts_resunit_f16_wide(const jatts_resunit_desc& d, hipStream_t s);    // C 
 int jatts_resunit_f32(const jatts_resunit_desc& d, hipStream_t s);
 int jatts_resunit_split(const jatts_resunit_desc& d, hipStream_t s);       // JATTS_F32S
 int jatts_resunit_emul(const jatts_resunit_desc& d, hipStream_t s, int* pick);   // JATTS_F32E (pick: report the form, launch nothing)
+int jatts_resunit1_f16(const jatts_resunit_desc& d, hipStream_t s);        // the single-conv unit (w2 == NULL): resunit1_*.hip
+int jatts_resunit1_f32(const jatts_resunit_desc& d, hipStream_t s);
+int jatts_resunit1_emul(const jatts_resunit_desc& d, hipStream_t s);       // JATTS_F32E / JATTS_F32E6, w_layout = 1
 int jatts_resblock_f16(const jatts_resblock_desc& d, hipStream_t s);
 int jatts_resblock_f32(const jatts_resblock_desc& d, hipStream_t s);
 int jatts_resblock_split(const jatts_resblock_desc& d, hipStream_t s);     // JATTS_F32S
@@ -74,18 +77,49 @@ extern "C" int jatts_conv1d(const jatts_conv_desc* d, void* stream) {
 }
 
 static int resunit_check(const jatts_resunit_desc* d) {
-  if (!d || !d->x || !d->y || !d->w1 || !d->w2 || !d->b1 || !d->b2 || !d->rg.cu_rows)
+  if (!d || !d->x || !d->y || !d->w1 || !d->b1 || !d->rg.cu_rows) return jatts_set_error_msg(JATTS_ERR_ARG, "resunit: null pointer");
+  if (!d->w2) {   // the single-conv unit
+    if (d->b2 || d->ws2) return jatts_set_error_msg(JATTS_ERR_ARG, "resunit: w2 == NULL (single-conv unit) takes b2 == NULL and ws2 == NULL");
+  } else if (!d->b2) {
     return jatts_set_error_msg(JATTS_ERR_ARG, "resunit: null pointer");
+  }
   if (d->x == d->y) return jatts_set_error_msg(JATTS_ERR_ARG, "resunit: y must not alias x");
   if (d->k_w < 1 || !(d->k_w & 1) || d->dil < 1) return jatts_set_error_msg(JATTS_ERR_ARG, "resunit: odd k_w and dil>=1 required");
   if (!(d->slope >= 0.f && d->slope <= 1.f)) return jatts_set_error_msg(JATTS_ERR_ARG, "resunit: LeakyReLU slope must be in [0, 1]");
   return JATTS_OK;
 }
 
+extern "C" int jatts_resunit_single_conv(int32_t dtype, int32_t w_layout) {
+  if (dtype == JATTS_F32 || dtype == JATTS_F16) return w_layout == 0;
+  return (dtype == JATTS_F32E || dtype == JATTS_F32E6) && w_layout == 1;
+}
+
+// The single-conv unit's arithmetics, checked before anything launches (an empty batch included): JATTS_F32, JATTS_F16 and the w_layout = 1 emulated forms.
+static int resunit1_check(const jatts_resunit_desc* d) {
+  if (d->dtype == JATTS_F32S)
+    return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: the single-conv unit (w2 == NULL) has no JATTS_F32S kernel (JATTS_F32 / JATTS_F16 / JATTS_F32E / JATTS_F32E6)");
+  if (d->dtype == JATTS_F32E || d->dtype == JATTS_F32E6) {
+    if (d->w_layout != 0 && d->w_layout != 1) return jatts_set_error_msg(JATTS_ERR_ARG, "resunit: w_layout must be 0 or 1");
+    if (d->w_layout != 1)
+      return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: the emulated single-conv unit (w2 == NULL) takes w_layout = 1 weights only");
+    return JATTS_OK;
+  }
+  if (d->w_layout != 0) return jatts_set_error_msg(JATTS_ERR_ARG, "resunit: w_layout = 1 goes with JATTS_F32E / JATTS_F32E6 only");
+  if (d->dtype != JATTS_F16 && d->dtype != JATTS_F32) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: unsupported channels/dtype (use jatts_conv1d)");
+  return JATTS_OK;
+}
+
 extern "C" int jatts_hifigan_resunit(const jatts_resunit_desc* d, void* stream) {
   if (const int rc = resunit_check(d)) return rc;
-  if (d->rg.max_len <= 0) return JATTS_OK;
   hipStream_t s = (hipStream_t)stream;
+  if (!d->w2) {
+    if (const int rc = resunit1_check(d)) return rc;
+    if (d->rg.max_len <= 0) return JATTS_OK;
+    if (d->dtype == JATTS_F16) return jatts_resunit1_f16(*d, s);
+    if (d->dtype == JATTS_F32) return jatts_resunit1_f32(*d, s);
+    return jatts_resunit1_emul(*d, s);
+  }
+  if (d->rg.max_len <= 0) return JATTS_OK;
   if (d->dtype == JATTS_F16) return d->channels <= 64 ? jatts_resunit_f16_narrow(*d, s) : jatts_resunit_f16_wide(*d, s);
   if (d->dtype == JATTS_F32) return jatts_resunit_f32(*d, s);
   if (d->dtype == JATTS_F32S) {
@@ -103,6 +137,10 @@ extern "C" int jatts_hifigan_resunit(const jatts_resunit_desc* d, void* stream) 
 extern "C" int jatts_resunit_variant(const jatts_resunit_desc* d) {
   if (const int rc = resunit_check(d)) return rc;
   int form = 1;                // every kernel but the 16 x 16 x 32 emulated units is windowed only
+  if (!d->w2) {                // the single-conv unit carries no h halo: windowed whatever `variant` asks
+    const int rc = resunit1_check(d);
+    return rc ? rc : 1;
+  }
   if (d->rg.max_len > 0 && (d->dtype == JATTS_F32E || d->dtype == JATTS_F32E6)) {
     if (d->w_layout != 0 && d->w_layout != 1) return jatts_set_error_msg(JATTS_ERR_ARG, "resunit: w_layout must be 0 or 1");
     if (const int rc = jatts_resunit_emul(*d, nullptr, &form)) return rc;

@@ -725,12 +725,14 @@ def _resunit_desc(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, 
     if x.numel() != rows * channels or y.numel() != rows * channels or x.dtype != torch_dtype(dtype):
         raise ValueError("hifigan_resunit: bad buffer size/dtype")
     d.x, d.y = _dev(x).data_ptr(), y.data_ptr()
-    _check_unit_weights("hifigan_resunit", dtype, channels, k_w, w1, w2)
-    d.w1, d.b1, d.w2, d.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
+    # w2 None: the single-conv unit (use_additional_convs=False) -- w2 / b2 / ws2 go down as NULL and the library checks that they agree
+    _check_unit_weights("hifigan_resunit", dtype, channels, k_w, *((w1,) if w2 is None else (w1, w2)))
+    d.w1, d.b1, d.w2, d.b2 = w1.data_ptr(), b1.data_ptr(), _ptr(w2), _ptr(b2)
     if dtype == F32S:
-        if ws is None or ws[0].numel() < channels or ws[1].numel() < channels or ws[0].dtype != torch.float32:
+        need = ws[:1] if ws is not None and w2 is None else ws      # (the single-conv unit has no F32S kernel: the library refuses it)
+        if need is None or any(v is None or v.numel() < channels or v.dtype != torch.float32 for v in need):
             raise ValueError("hifigan_resunit: F32S needs the inverse weight scales (pack_conv_weight_split)")
-        d.ws1, d.ws2 = ws[0].data_ptr(), ws[1].data_ptr()
+        d.ws1, d.ws2 = ws[0].data_ptr(), _ptr(ws[1]) if len(ws) > 1 else None
     if add:
         for a in add:
             if a.numel() != rows * channels or a.dtype != x.dtype:
@@ -742,7 +744,8 @@ def _resunit_desc(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, 
 
 
 def hifigan_resunit(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, dtype, add=None, out_scale=1.0, ws=None, w_layout=0, variant=0):
-    """jatts_hifigan_resunit.  w_layout (F32E / F32E6): 0 = weights from pack_conv_weight_bf16x3(w, 32) (32 x 32 x 16 kernels), 1 = from
+    """jatts_hifigan_resunit.  w2 = b2 = None: the single-conv unit y = x + conv_k,d(lrelu(x)) + b1 (F32, F16, F32E / F32E6 with w_layout 1).
+    w_layout (F32E / F32E6): 0 = weights from pack_conv_weight_bf16x3(w, 32) (32 x 32 x 16 kernels), 1 = from
     pack_unit_weight_bf16x3_k32 (16 x 16 x 32 kernels).  variant (jatts_resunit_desc.variant): 0 = the library's choice, 1 = windowed, 2 = sliding."""
     lib = _abi.load()
     d = _resunit_desc(rb, len_mul, x, y, w1, b1, w2, b2, channels, k_w, dil, slope, dtype, add, out_scale, ws, w_layout, variant)

@@ -146,6 +146,9 @@ HIFIGAN_V1_22K = dict(  # parallel_wavegan HiFiGANGenerator defaults [recalled]:
     use_weight_norm=True,
 )
 HIFIGAN_V1_24K = dict(HIFIGAN_V1_22K, upsample_scales=(5, 5, 4, 3), upsample_kernel_sizes=(10, 10, 8, 6))
+# HiFi-GAN V3 (arXiv 2010.05646 App. A): 256 channels, three stages, ResBlocks of two single-conv dilation units (no convs2)
+HIFIGAN_V3_22K = dict(HIFIGAN_V1_22K, channels=256, upsample_scales=(8, 8, 4), upsample_kernel_sizes=(16, 16, 8),
+                      resblock_kernel_sizes=(3, 5, 7), resblock_dilations=((1, 2), (2, 6), (3, 12)), use_additional_convs=False)
 
 
 def synth_hifigan_state(params, seed=0, gain=1.0):
@@ -163,18 +166,22 @@ def synth_hifigan_state(params, seed=0, gain=1.0):
     rn("input_conv.weight", (ch, params["in_channels"], k), params["in_channels"] * k)
     rn("input_conv.bias", (ch,))
     nb = len(params["resblock_kernel_sizes"])
+    bias = params.get("bias", True)      # False: the transposed and ResBlock convs have none (input / output convs keep theirs)
     c = ch
     for i, (us, uk) in enumerate(zip(params["upsample_scales"], params["upsample_kernel_sizes"])):
         rn(f"upsamples.{i}.1.weight", (c, c // 2, uk), c * uk / us)
-        rn(f"upsamples.{i}.1.bias", (c // 2,))
+        if bias:
+            rn(f"upsamples.{i}.1.bias", (c // 2,))
         c //= 2
         for j, rk in enumerate(params["resblock_kernel_sizes"]):
             for d in range(len(params["resblock_dilations"][j])):
                 rn(f"blocks.{i * nb + j}.convs1.{d}.1.weight", (c, c, rk), c * rk)
-                rn(f"blocks.{i * nb + j}.convs1.{d}.1.bias", (c,))
+                if bias:
+                    rn(f"blocks.{i * nb + j}.convs1.{d}.1.bias", (c,))
                 if params.get("use_additional_convs", True):
                     rn(f"blocks.{i * nb + j}.convs2.{d}.1.weight", (c, c, rk), c * rk, 0.3)
-                    rn(f"blocks.{i * nb + j}.convs2.{d}.1.bias", (c,))
+                    if bias:
+                        rn(f"blocks.{i * nb + j}.convs2.{d}.1.bias", (c,))
     rn("output_conv.1.weight", (params["out_channels"], c, k), c * k, 0.5)
     rn("output_conv.1.bias", (params["out_channels"],))
     return sd

@@ -1,4 +1,4 @@
-"""HiFi-GAN v1 generator on the MI355X HIP path.
+"""HiFi-GAN generator (V1 / V2 / V3 configurations) on the MI355X HIP path.
 
 Drop-in for ``parallel_wavegan.models.HiFiGANGenerator`` as the reference uses it
 (/root/reference/jatts/vocoder/vocoder.py:41-44,64): same constructor kwargs and
@@ -10,6 +10,8 @@ entry: one packed ragged batch of mels -> packed waveforms.
 Kernel schedule per batch: affine/cast -> input conv (MFMA implicit GEMM) -> per
 upsample stage [polyphase ConvTranspose as MFMA conv (LeakyReLU + MRF mean fused on the
 input side) -> 3 ResBlocks x 3 fused dilation units] -> output conv + tanh.
+``use_additional_convs=False`` (HiFi-GAN V3): the units are the single-conv form
+x + conv_k,d(lrelu(x)) (csrc/resunit1_*); ``bias=False``: no bias in the transposed and ResBlock convs.
 """
 
 import torch
@@ -52,8 +54,7 @@ class HiFiGANGenerator(torch.nn.Module):
             raise NotImplementedError("only LeakyReLU generators are supported")
         if out_channels != 1:
             raise NotImplementedError("out_channels must be 1")
-        if not use_additional_convs or not bias:
-            raise NotImplementedError("use_additional_convs=True and bias=True required (HiFi-GAN v1)")
+        self.use_additional_convs, self.bias = bool(use_additional_convs), bool(bias)
         if len(upsample_scales) != len(upsample_kernel_sizes):
             raise ValueError("upsample_scales / upsample_kernel_sizes mismatch")
         self.slope = float((nonlinear_activation_params or {"negative_slope": 0.1}).get("negative_slope", 0.1))
@@ -78,12 +79,14 @@ class HiFiGANGenerator(torch.nn.Module):
         c = channels
         for i, uk in enumerate(self.upsample_kernel_sizes):
             spec[f"upsamples.{i}.1.weight"] = ((c, c // 2, uk), "param")
-            spec[f"upsamples.{i}.1.bias"] = ((c // 2,), "param")
+            if self.bias:      # (input_conv / output_conv keep theirs)
+                spec[f"upsamples.{i}.1.bias"] = ((c // 2,), "param")
             c //= 2
             for j, rk in enumerate(self.resblock_kernel_sizes):
                 for d in range(len(self.resblock_dilations[j])):
-                    S._conv(spec, f"blocks.{i * nb + j}.convs1.{d}.1", c, c, rk)
-                    S._conv(spec, f"blocks.{i * nb + j}.convs2.{d}.1", c, c, rk)
+                    S._conv(spec, f"blocks.{i * nb + j}.convs1.{d}.1", c, c, rk, bias=self.bias)
+                    if self.use_additional_convs:
+                        S._conv(spec, f"blocks.{i * nb + j}.convs2.{d}.1", c, c, rk, bias=self.bias)
         S._conv(spec, "output_conv.1", out_channels, c, kernel_size)
         S.build_from_spec(self, spec)
         self.precision = "fp32"   # the reference's arithmetic; set_precision("fp16") selects the fast mode
@@ -121,6 +124,9 @@ class HiFiGANGenerator(torch.nn.Module):
         conv1d_emul.h); "fp32_bf16x3_6p": six products (JATTS_F32E6: dropped terms <= 2^-23 per product, 1/7 fewer pipe cycles)."""
         if precision not in hip.PRECISIONS:
             raise ValueError(precision)
+        if precision == "fp32_split" and not self.use_additional_convs:
+            raise NotImplementedError("fp32_split (JATTS_F32S) has no single-conv dilation unit: generators with use_additional_convs=False run in "
+                                      "fp32, fp16, fp32_bf16x3 or fp32_bf16x3_6p")
         if precision != self.precision:
             self.precision, self._prep = precision, None
         return self
@@ -163,9 +169,10 @@ class HiFiGANGenerator(torch.nn.Module):
             o[: w.shape[0], : w.shape[1]] = w
             return o
 
-        def padb(b, n):
+        def padb(b, n):      # b None (bias=False): the zero vector
             o = torch.zeros(n, dtype=torch.float32)
-            o[: b.numel()] = b.detach().float()
+            if b is not None:
+                o[: b.numel()] = b.detach().float()
             return o
 
         c_prev = hip.round_up(self.channels, 64)   # input conv feeds the generic conv: 64-channel chunks
@@ -181,7 +188,7 @@ class HiFiGANGenerator(torch.nn.Module):
             wp[: w.shape[0], : w.shape[1]] = w
             wc, pad = hip.convtranspose_as_conv(wp, s, s // 2 + s % 2)
             with hip.split_weights(wmode):
-                pc = PackedConv(wc, padb(sd[f"upsamples.{i}.1.bias"], c_out).repeat(s), dt, dev)
+                pc = PackedConv(wc, padb(sd.get(f"upsamples.{i}.1.bias"), c_out).repeat(s), dt, dev)
             P["ups"].append((pc, pad, s, c_out))
             stage = []
             for j, rk in enumerate(self.resblock_kernel_sizes):
@@ -191,10 +198,13 @@ class HiFiGANGenerator(torch.nn.Module):
                     # the units' weights in the fragment order of the v_mfma_f32_16x16x32_bf16 kernels (round 6: the power-limited matrix pipe sustains
                     # 14 % more of that form, csrc/resunit_emul16_impl.h); the fused ResBlock launches take the 32 x 32 x 16 form (also32)
                     k32 = c_out % 32 == 0
-                    mk = (PackedSplitConv if split else (lambda w, b: PackedEmulConv(w, b, k32, (c_out, rk) in self.fused_blocks_emul)) if emul
+                    also32 = self.use_additional_convs and (c_out, rk) in self.fused_blocks_emul     # (single-conv blocks are never fused)
+                    mk = (PackedSplitConv if split else (lambda w, b: PackedEmulConv(w, b, k32, also32)) if emul
                           else (lambda w, b: PackedConv(w, b, dt, dev, c_mult=32)))   # fused unit takes c_in == channels
-                    c1 = mk(padw(sd[q + f"convs1.{di}.1.weight"], c_out, c_out).to(dev), padb(sd[q + f"convs1.{di}.1.bias"], c_out).to(dev))
-                    c2 = mk(padw(sd[q + f"convs2.{di}.1.weight"], c_out, c_out).to(dev), padb(sd[q + f"convs2.{di}.1.bias"], c_out).to(dev))
+                    c1 = mk(padw(sd[q + f"convs1.{di}.1.weight"], c_out, c_out).to(dev), padb(sd.get(q + f"convs1.{di}.1.bias"), c_out).to(dev))
+                    # use_additional_convs=False: the single-conv unit, convs1 only
+                    c2 = mk(padw(sd[q + f"convs2.{di}.1.weight"], c_out, c_out).to(dev), padb(sd.get(q + f"convs2.{di}.1.bias"), c_out).to(dev)) \
+                        if self.use_additional_convs else None
                     units.append((c1, c2, rk, d))
                 stage.append(units)
             P["blocks"].append(stage)
@@ -267,7 +277,7 @@ class HiFiGANGenerator(torch.nn.Module):
                 # HBM-bound shapes: the whole ResBlock in one launch (x read once, y written once; residual in registers)
                 fset = (self.fused_blocks_split if udt == hip.F32S else self.fused_blocks_emul if udt in hip.EMUL
                         else (self.fused_blocks if dt == hip.F16 else self.fused_blocks_f32))
-                if (c_out, units[0][2]) in fset and len(units) <= 3 \
+                if self.use_additional_convs and (c_out, units[0][2]) in fset and len(units) <= 3 \
                         and sum((units[0][2] - 1) // 2 * (u[3] + 1) for u in units) <= (64 if (dt == hip.F16 or udt == hip.F32S or udt in hip.EMUL) else 16):
                     lastb = fuse_mean and j == len(blocks) - 1
                     hip.hifigan_resblock(rb, rate, cur, bufs[j][0], [(getattr(c1, "w32", c1.w), c1.b, getattr(c2, "w32", c2.w), c2.b, d) for c1, c2, _, d in units],
@@ -281,7 +291,8 @@ class HiFiGANGenerator(torch.nn.Module):
                     # (c_out is always a fused-unit width: _prepare zero-pads narrower stages and refuses wider ones)
                     last = fuse_mean and j == len(blocks) - 1 and di == len(units) - 1
                     # the last unit of the last ResBlock writes the MRF mean (cs / num_blocks) directly
-                    hip.hifigan_resunit(rb, rate, cur, nxt, c1.w, c1.b, c2.w, c2.b, c_out, rk, d, self.slope, udt,
+                    # (c2 None: the single-conv unit of a generator without the additional convs)
+                    hip.hifigan_resunit(rb, rate, cur, nxt, c1.w, c1.b, c2.w if c2 else None, c2.b if c2 else None, c_out, rk, d, self.slope, udt,
                                         add=outs if last else None, out_scale=1.0 / len(blocks) if last else 1.0,
                                         ws=(c1.inv, c2.inv) if udt == hip.F32S else None, w_layout=getattr(c1, "layout", 0))
                     cur = nxt

@@ -2,7 +2,8 @@
 """Micro-benchmark of the fused HiFi-GAN dilation-unit kernel at bench-sized shapes.
     python tools/bench_unit.py [--C 128 --k 11 --dil 1 --iters 10] [--all] [--variant 0|1|2 | --variants]
 Prints avg ms, TFLOP/s and algorithmic GB/s per shape (HIP events on the launch stream).  --variants (emulated units): the windowed and the sliding
-form of every shape side by side (jatts_resunit_desc.variant 1 / 2)."""
+form of every shape side by side (jatts_resunit_desc.variant 1 / 2).  --single: the SINGLE-CONV unit (w2 = None; HiFi-GAN V3 shapes) against the two-conv unit of
+the same shape, alternating rounds in one process, with the share of the binding roof."""
 import argparse
 import os
 import sys
@@ -106,6 +107,65 @@ def run_block(C, k, rate, iters, B=64, T=768, dils=(1, 3, 5), dt=hip.F16):
     return res
 
 
+# Roofs of the --single table: HBM as a float4 copy measures it; the matrix pipe at its nominal f32 / f16 rates, the emulated arithmetic at the sustained
+# v_mfma_f32_16x16x32_bf16 rate on random operands (csrc/resunit_emul16_impl.h) over its seven / six MFMAs per product
+HBM_GBS = 6290.0
+PIPE_TFLOPS = {hip.F32: 157.3, hip.F16: 2516.0, hip.F32E: 1798.0 / 7, hip.F32E6: 1798.0 / 6}
+V3_SHAPES = [(C, k, d) for C in (128, 64, 32) for k, ds in ((3, (1, 2)), (5, (2, 6)), (7, (3, 12))) for d in ds]
+V3_RATES = {128: 8, 64: 64, 32: 256}       # HiFi-GAN V3 22.05 kHz stage rates (upsample scales 8, 8, 4)
+
+
+def run_single(C, k, d, rate, iters, rounds=5, B=64, T=768, dtype=hip.F16):
+    """Single-conv unit (w2 = None) and the two-conv unit of the same (C, k, d, rows, dtype): `rounds` alternating timings of `iters` launches each.
+    Prints the medians, the two-conv unit's own spread (max - min over its rounds), algorithmic TFLOP/s (2 C^2 k rows) and GB/s (2 rows C sizeof) of the
+    single-conv unit and its share of the roof that binds."""
+    dev = torch.device("cuda:0")
+    rb = hip.RaggedBatch([T] * B, dev)
+    rows = B * T * rate
+    g = torch.Generator(device="cpu").manual_seed(0)
+    x = torch.randn(rows, C, generator=g).to(dev).to(hip.torch_dtype(dtype))
+    y = torch.empty_like(x)
+    wa, wb = (torch.randn(C, C, k, generator=g) / (C * k) ** 0.5).to(dev), (torch.randn(C, C, k, generator=g) / (C * k) ** 0.5).to(dev)
+    kw = {}
+    if dtype in hip.EMUL:
+        w1, w2 = hip.pack_unit_weight_bf16x3_k32(wa), hip.pack_unit_weight_bf16x3_k32(wb)
+        kw["w_layout"] = 1
+    else:
+        w1, w2 = hip.pack_conv_weight(wa, dtype, 32), hip.pack_conv_weight(wb, dtype, 32)
+    b1, b2 = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
+    forms = {"two": lambda: hip.hifigan_resunit(rb, rate, x, y, w1, b1, w2, b2, C, k, d, 0.1, dtype, **kw),
+             "one": lambda: hip.hifigan_resunit(rb, rate, x, y, w1, b1, None, None, C, k, d, 0.1, dtype, **kw)}
+    ms = {"two": [], "one": []}
+    try:
+        forms["two"]()
+    except hip._abi.JattsHipError:      # no two-conv tile for this window (exact f32, C = 128, (k - 1) dil = 72): nothing to compare with
+        del forms["two"], ms["two"]
+    for fn in forms.values():
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for name, fn in forms.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms[name].append(a.elapsed_time(b) / iters)
+    med = {n: sorted(v)[len(v) // 2] for n, v in ms.items()}
+    spread = max(ms["two"]) - min(ms["two"]) if "two" in ms else 0.0
+    tf = 2.0 * C * C * k * rows / med["one"] / 1e9
+    gbs = 2.0 * rows * C * x.element_size() / med["one"] / 1e6
+    share = {"matrix": tf / PIPE_TFLOPS[dtype], "HBM": gbs / HBM_GBS}
+    roof = max(share, key=share.get)
+    med.setdefault("two", float("nan"))    # (refused)
+    verdict = "SLOWER" if med["one"] > med["two"] + spread else "ok"
+    print(f"C={C:4d} k={k:2d} d={d:2d} rows={rows:9d}  single {med['one']:7.3f} ms  two-conv {med['two']:7.3f} ms (spread {spread:.3f})  "
+          f"{tf:7.1f} TFLOP/s  {gbs:7.1f} GB/s  {share[roof]:.2f} of the {roof} roof  {verdict}")
+    return med
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--C", type=int, default=128)
@@ -119,10 +179,20 @@ def main():
     ap.add_argument("--layout", type=int, default=1, choices=[0, 1], help="emulated units: 1 = v_mfma_f32_16x16x32_bf16 kernels (product), 0 = 32x32x16")
     ap.add_argument("--variant", type=int, default=0, choices=[0, 1, 2], help="emulated units, layout 1: 0 = the library's form, 1 = windowed, 2 = sliding")
     ap.add_argument("--variants", action="store_true", help="emulated units, layout 1: time the windowed and the sliding form of every shape")
+    ap.add_argument("--single", action="store_true", help="single-conv unit (w2 = None) vs the two-conv unit at the HiFi-GAN V3 shapes (f32 / emul / emul6 / f16)")
     a = ap.parse_args()
     rates = {256: 8, 128: 64, 64: 128, 32: 256}  # HiFi-GAN v1 22.05 kHz stage rates
     dt = {"f16": hip.F16, "f32": hip.F32, "split": hip.F32S, "emul": hip.F32E, "emul6": hip.F32E6}[a.dtype]
     LAYOUT[0] = a.layout
+    if a.single:
+        if dt == hip.F32S:
+            ap.error("--single: the split arithmetic has no single-conv unit")
+        tot = {"one": 0.0, "two": 0.0}
+        for C, k, d in V3_SHAPES:
+            med = run_single(C, k, d, V3_RATES[C], a.iters, B=a.batch, dtype=dt)
+            tot = {n: tot[n] + med[n] for n in tot}       # (two-conv: nan once a shape was refused)
+        print(f"sum over the 18 units of one V3 generator pass: single {tot['one']:.2f} ms, two-conv {tot['two']:.2f} ms")
+        return
     if a.resblock:
         for C in ((32, 64, 128) if dt == hip.F16 else (32, 64)):
             for k in ((3, 7) if dt != hip.F32 else (3,)):
