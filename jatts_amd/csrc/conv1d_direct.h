@@ -21,9 +21,7 @@
 // (lane & 31) = 8 consecutive channels 16 kc + 8 (lane >> 5) .. of row pos (two 16-byte loads per lane).
 #pragma once
 #include "conv1d_impl.h"
-
-extern unsigned long long* jatts_g_trace;  // profiling hook (conv_api.hip: jatts_debug_trace)
-extern unsigned jatts_g_trace_cap;
+#include "unit_frame.h"
 
 namespace {
 
@@ -55,21 +53,10 @@ __device__ __forceinline__ void apply_act_alpha(f32x16 (&acc)[NF][NT], int act, 
 // made the register allocator spill an accumulator fragment inside the main loop of EVERY launch.
 template <int NF, int NT, int WN, int WT, int D, int DIAG = 0, bool PRE = false, bool SNAKE = false>
 __global__ __launch_bounds__(WN* WT * 64, (D <= 2 ? 3 : 2)) void conv1d_direct_kernel(jatts_conv_desc d, unsigned long long* trace, unsigned trace_cap, XcdOrder xo) {
-  const unsigned wg_lin = blockIdx.x;     // 1-D grid in XCD-aware order (conv1d_impl.h: XcdOrder)
   int bx, by, bz;
-  if (!xo.decode(wg_lin, bx, by, bz, d.rg, WT * NT * 32)) return;
-  // Phase trace (profiling hook, jatts_debug_trace; tools/trace_conv.py): thread 0 of the first trace_cap workgroups stamps
-  // [hw id, start, main loop entered, main loop done, stored, -, -, -, realtime start, realtime end]
-  const bool tracing = trace != nullptr && wg_lin < trace_cap && threadIdx.x == 0;
-#define JATTS_CSTAMP(i) do { if (tracing) trace[(size_t)wg_lin * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-  if (tracing) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    trace[(size_t)wg_lin * 16] = ((unsigned long long)xcc << 32) | hwid;
-    trace[(size_t)wg_lin * 16 + 8] = __builtin_amdgcn_s_memrealtime();
-  }
-  JATTS_CSTAMP(1);
+  if (!xo.decode(blockIdx.x, bx, by, bz, d.rg, WT * NT * 32)) return;     // 1-D grid in XCD-aware order (conv1d_impl.h: XcdOrder)
+  // phase stamps: 1 start, 2 main loop entered, 3 main loop done, 4 stored (tools/trace_conv.py)
+  JATTS_TRACE_BEGIN(trace, trace_cap, blockIdx.x);
   constexpr int BT = WT * NT * 32;
   const int b = by;
   const int row_b = d.rg.cu_rows[b];
@@ -138,7 +125,7 @@ __global__ __launch_bounds__(WN* WT * 64, (D <= 2 ? 3 : 2)) void conv1d_direct_k
   for (int j = 0; j < D; ++j) issue(ra[j], rb[j]);
   __builtin_amdgcn_sched_barrier(0);
   const int n_steps = KC16 * d.k_w;   // a multiple of 4 (c_in % 64 == 0), hence of D
-  JATTS_CSTAMP(2);
+  JATTS_STAMP(2);
   for (int s0 = 0; s0 < n_steps; s0 += D) {
 #pragma unroll
     for (int j = 0; j < D; ++j) {
@@ -156,7 +143,7 @@ __global__ __launch_bounds__(WN* WT * 64, (D <= 2 ? 3 : 2)) void conv1d_direct_k
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  JATTS_CSTAMP(3);
+  JATTS_STAMP(3);
 
   // Row-major f32 outputs (every projection / FFN / postnet conv): fragment-order epilogue through buffer stores -- a lane owns 4
   // consecutive channels of one row (16 bytes), its g-neighbour the next 4; rows past the sequence end are dropped by the range
@@ -198,9 +185,8 @@ __global__ __launch_bounds__(WN* WT * 64, (D <= 2 ? 3 : 2)) void conv1d_direct_k
       default: conv_epilogue<float, JATTS_ACT_NONE, NF, NT>(d, acc, t0, col0, nf0, lane, L, seq_row0, b); break;
     }
   }
-  JATTS_CSTAMP(4);
-  if (tracing) trace[(size_t)wg_lin * 16 + 9] = __builtin_amdgcn_s_memrealtime();
-#undef JATTS_CSTAMP
+  JATTS_STAMP(4);
+  JATTS_TRACE_END();
 }
 
 // Eligibility: one plain input (no sum / scale / LeakyReLU prologue), zero padding, 16-byte aligned rows, and sequence slabs /

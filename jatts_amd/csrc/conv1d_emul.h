@@ -9,6 +9,7 @@
 // the other feeds the matrix pipe; a chunk is k_w x 2 K-steps x 7 (6) NF NT MFMAs, 56 (48) MFMAs per wave between barriers at k = 1.
 #pragma once
 #include "conv1d_impl.h"
+#include "unit_frame.h"   // unit_lds_ready
 #ifndef JATTS_CEMUL_DIAG
 #define JATTS_CEMUL_DIAG 0   // timing probes only (wrong results): 1 = no split arithmetic in the commit, 2 = no activation loads in the chunk loop, 4 = no barriers in it;
                              // 16 x 16 x 32 kernel only: 8 = no weight refills, 16 = no B (LDS) refills, 32 = no epilogue, 64 = no commit at all
@@ -178,9 +179,8 @@ int launch_conv_emul(const jatts_conv_desc& d, hipStream_t s) {
     f32_tile = 1;
     if (lds < (size_t)BT * (BN * 4 + 16)) lds = (size_t)BT * (BN * 4 + 16);
   }
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d (emulated): tile exceeds 160 KiB LDS");
-  auto kern = conv1d_emul_kernel<T, NF, NT, WN, WT, NIN, KCHT, OCC, HALO, RD>;
-  JATTS_RAISE_LDS_LIMIT(kern);
+  constexpr auto kern = conv1d_emul_kernel<T, NF, NT, WN, WT, NIN, KCHT, OCC, HALO, RD>;
+  if (const int rc = unit_lds_ready<kern>(JATTS_SITE("conv1d (emulated): tile exceeds 160 KiB LDS"), lds)) return rc;
   XcdOrder xo;
   const int64_t total = xo.plan((int)grid.x, (int)grid.y, (int)grid.z, (int64_t)BN * d.c_in * d.k_w * 6, ragged_tiles_1d(d.rg, BT));
   if (total >= (int64_t)1 << 31) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d: launch too large");

@@ -11,6 +11,7 @@
 //  * epilogues on the 16 x 16 C / D layout (column = lane & 15, channels 4 (lane >> 4) + {0..3} of the fragment).
 #pragma once
 #include "conv1d_emul.h"
+#include "unit_frame.h"
 #include "resunit_emul16_impl.h"
 
 #ifndef JATTS_CEMUL_ANTIPHASE
@@ -347,9 +348,7 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void conv1d_emul16_kernel(jatts_c
     JATTS_PH(6);    // epilogue
     if (!tracing) return;
     unsigned long long* o = trace + (size_t)blockIdx.x * 16;
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    JATTS_TRACE_HWID(hwid, xcc);
     o[0] = ((unsigned long long)(xcc & 0xF) << 32) | hwid;
     for (int i = 0; i < 7; ++i) o[1 + i] = ph[i];
     o[8] = rt_begin; o[9] = __builtin_amdgcn_s_memrealtime(); o[10] = t_begin; o[11] = tq;
@@ -408,9 +407,8 @@ int launch_conv_emul16(const jatts_conv_desc& d, hipStream_t s) {
     f32_tile = 1;
     if (lds < (size_t)BT * (BN * 4 + 16)) lds = (size_t)BT * (BN * 4 + 16);
   }
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d (emulated): tile exceeds 160 KiB LDS");
-  auto kern = conv1d_emul16_kernel<T, NF, NT, WN, WT, NIN, KCHT, OCC, HALO, D>;
-  JATTS_RAISE_LDS_LIMIT(kern);
+  constexpr auto kern = conv1d_emul16_kernel<T, NF, NT, WN, WT, NIN, KCHT, OCC, HALO, D>;
+  if (const int rc = unit_lds_ready<kern>(JATTS_SITE("conv1d (emulated): tile exceeds 160 KiB LDS"), lds)) return rc;
   XcdOrder xo;
   const int64_t total = xo.plan((int)grid.x, (int)grid.y, (int)grid.z, (int64_t)BN * d.c_in * d.k_w * 6, ragged_tiles_1d(d.rg, BT));
   if (total >= (int64_t)1 << 31) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d: launch too large");

@@ -14,6 +14,7 @@
 #pragma once
 #include "conv1d_impl.h"
 #include "resunit_split_impl.h"   // split_exp / exp2i / block_amax
+#include "unit_frame.h"           // unit_lds_ready
 
 namespace {
 
@@ -198,9 +199,8 @@ int launch_conv_split(const jatts_conv_desc& d, hipStream_t s) {
   }
   const unsigned slot_off = (unsigned)lds;
   lds += 64;                                                              // one amax slot per wave
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d (split): tile exceeds 160 KiB LDS");
-  auto kern = conv1d_split_kernel<NF, NT, WN, WT, NIN, KCHT, OCC, HALO, RD>;
-  JATTS_RAISE_LDS_LIMIT(kern);
+  constexpr auto kern = conv1d_split_kernel<NF, NT, WN, WT, NIN, KCHT, OCC, HALO, RD>;
+  if (const int rc = unit_lds_ready<kern>(JATTS_SITE("conv1d (split): tile exceeds 160 KiB LDS"), lds)) return rc;
   XcdOrder xo;
   const int64_t total = xo.plan((int)grid.x, (int)grid.y, (int)grid.z, (int64_t)BN * d.c_in * d.k_w * 4, ragged_tiles_1d(d.rg, BT));
   if (total >= (int64_t)1 << 31) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d: launch too large");

@@ -13,6 +13,7 @@
 #pragma once
 #include <type_traits>
 
+#include "unit_frame.h"
 #include "resunit_impl.h"
 
 namespace {
@@ -53,13 +54,10 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC) void resblock_ke
     M = max(M, p2 * d.dil[u]);
   }
   const int tt_out = WGCOLS - 2 * H;
-  int b = blockIdx.y, bx = blockIdx.x;
-  if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, tt_out, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
-  const int row_b = d.rg.cu_rows[b];
-  const int L = (d.rg.cu_rows[b + 1] - row_b) * d.rg.len_mul;
-  const int t0 = bx * tt_out;
-  if (t0 >= L) return;
-  const int64_t seq_row0 = (int64_t)row_b * d.rg.len_mul;
+  unit_window win;
+  if (!unit_window_of(d.rg, tt_out, win)) return;
+  const int L = win.L, t0 = win.t0;
+  const int64_t seq_row0 = win.seq_row0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wn = wave / WT, wt = wave % WT;
   const int g = lane >> 5;
@@ -188,10 +186,7 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC) void resblock_ke
     const int vrows = min(tt_out, L - t0);
     const int64_t g0 = (seq_row0 + t0) * (int64_t)C;
     const char* ys = smem + (size_t)(M + H) * pitch;
-    T* yg = (T*)d.y;
-    constexpr bool keep_small = C <= 64;
-    if (d.add0) unit_store_pass<T, C, keep_small ? 2 : 4, true, NTHR, false>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
-    else unit_store_pass<T, C, keep_small ? 4 : 8, false, NTHR, false>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
+    unit_store<T, C, NTHR, false>(d, ys, pitch, vrows, g0);   // (the residual is in the tile already)
   }
 }
 
@@ -210,15 +205,8 @@ int launch_resblock(const jatts_resblock_desc& d, hipStream_t s) {
   size_t lds = (size_t)(WGCOLS + 2 * M) * pitch;
   const unsigned bias_off = (unsigned)lds;
   lds += (size_t)d.n_units * 2 * C * sizeof(float);
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resblock: tile exceeds 160 KiB LDS");
-  const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
-  dim3 grid((unsigned)((maxL + tt_out - 1) / tt_out), (unsigned)d.rg.n_seq);
-  if (const int64_t n1 = ragged_tiles_1d(d.rg, tt_out)) grid = dim3((unsigned)n1);
-  auto kern = resblock_kernel<T, C, WGCOLS, WN, NT, KCGMAX, OCC>;
-  JATTS_RAISE_LDS_LIMIT(kern);
-  hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, bias_off);
-  JATTS_CHECK_LAUNCH();
-  return JATTS_OK;
+  constexpr auto kern = resblock_kernel<T, C, WGCOLS, WN, NT, KCGMAX, OCC>;
+  return unit_launch<kern>(JATTS_SITE("resblock: tile exceeds 160 KiB LDS"), WN * WT * 64, lds, tt_out, d.rg, s, d, bias_off);
 }
 
 }  // namespace

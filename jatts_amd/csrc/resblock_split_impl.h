@@ -8,6 +8,7 @@
 // per unit -- the per-unit split launches of C = 32, k = 3 already sit at 3.7 TB/s of x-in + y-out.
 // The block-maximum exchanges ride on barriers the chain needs anyway (the tile hand-offs between convs).
 #pragma once
+#include "unit_frame.h"
 #include "resblock_impl.h"
 #include "resunit_split_impl.h"
 
@@ -32,13 +33,10 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC) void resblock_sp
     M = max(M, p2 * d.dil[u]);
   }
   const int tt_out = WGCOLS - 2 * H;
-  int b = blockIdx.y, bx = blockIdx.x;
-  if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, tt_out, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
-  const int row_b = d.rg.cu_rows[b];
-  const int L = (d.rg.cu_rows[b + 1] - row_b) * d.rg.len_mul;
-  const int t0 = bx * tt_out;
-  if (t0 >= L) return;
-  const int64_t seq_row0 = (int64_t)row_b * d.rg.len_mul;
+  unit_window win;
+  if (!unit_window_of(d.rg, tt_out, win)) return;
+  const int L = win.L, t0 = win.t0;
+  const int64_t seq_row0 = win.seq_row0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wn = wave / WT, wt = wave % WT;
   const int g = lane >> 5;
@@ -226,10 +224,7 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC) void resblock_sp
     const int vrows = min(tt_out, L - t0);
     const int64_t g0 = (seq_row0 + t0) * (int64_t)C;
     const char* ys = smem + (size_t)(M + H) * pitch;
-    float* yg = (float*)d.y;
-    constexpr bool keep_small = C <= 64;
-    if (d.add0) unit_store_pass<float, C, keep_small ? 2 : 4, true, NTHR, false>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
-    else unit_store_pass<float, C, keep_small ? 4 : 8, false, NTHR, false>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
+    unit_store<float, C, NTHR, false>(d, ys, pitch, vrows, g0);   // (the residual is in the tile already)
   }
 }
 
@@ -249,15 +244,8 @@ int launch_resblock_split(const jatts_resblock_desc& d, hipStream_t s) {
   size_t lds = (size_t)(WGCOLS + 2 * M) * pitch;
   const unsigned bias_off = (unsigned)lds;
   lds += (size_t)d.n_units * 4 * C * sizeof(float) + 64;
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resblock (split): tile exceeds 160 KiB LDS");
-  const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
-  dim3 grid((unsigned)((maxL + tt_out - 1) / tt_out), (unsigned)d.rg.n_seq);
-  if (const int64_t n1 = ragged_tiles_1d(d.rg, tt_out)) grid = dim3((unsigned)n1);
-  auto kern = resblock_split_kernel<C, WGCOLS, WN, NT, KCG, OCC>;
-  JATTS_RAISE_LDS_LIMIT(kern);
-  hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, bias_off);
-  JATTS_CHECK_LAUNCH();
-  return JATTS_OK;
+  constexpr auto kern = resblock_split_kernel<C, WGCOLS, WN, NT, KCG, OCC>;
+  return unit_launch<kern>(JATTS_SITE("resblock (split): tile exceeds 160 KiB LDS"), WN * WT * 64, lds, tt_out, d.rg, s, d, bias_off);
 }
 
 }  // namespace

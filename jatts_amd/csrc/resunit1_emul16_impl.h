@@ -31,11 +31,12 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit1_emul16_kernel(jatts
   const int K = d.k_w, dil = d.dil;
   const int p1 = (K - 1) / 2 * dil;
 
-  int bx = blockIdx.x, b = blockIdx.y;
+  // unit_window_of (unit_frame.h), kept as this kernel's own copy: timed slower than the parent at some shapes with the helper (profiles/r14_notes.md)
+  int b = blockIdx.y, bx = blockIdx.x;
   if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, WGCOLS, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
-  const int t0 = bx * WGCOLS;
   const int row_b = d.rg.cu_rows[b];
   const int L = (d.rg.cu_rows[b + 1] - row_b) * d.rg.len_mul;
+  const int t0 = bx * WGCOLS;
   if (t0 >= L) return;
   const int64_t seq_row0 = (int64_t)row_b * d.rg.len_mul;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -199,10 +200,8 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit1_emul16_kernel(jatts
   __syncthreads();
   {
     const int64_t g0 = (seq_row0 + t0) * (int64_t)C;
-    constexpr bool keep_small = C <= 64;
-    const float* xg = (const float*)d.x;
-    float* yg = (float*)d.y;
     if constexpr (RREG) {
+      float* yg = (float*)d.y;
       constexpr int UPR = C / 8;
       const int n_out = nvalid * UPR;
       const bool has_add1 = d.add0 != nullptr && d.add1 != nullptr;
@@ -234,8 +233,7 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit1_emul16_kernel(jatts
         *reinterpret_cast<f32x4*>(dst + 4) = f32x4{o[4], o[5], o[6], o[7]};
       }
     } else {
-      if (d.add0) unit_store_pass<float, C, keep_small ? 2 : 4, true, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch_y, nvalid, xg, yg, g0);
-      else unit_store_pass<float, C, keep_small ? 4 : 8, false, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch_y, nvalid, xg, yg, g0);
+      unit_store<float, C, NTHR>(d, ys, pitch_y, nvalid, g0);
     }
   }
 }
@@ -253,15 +251,8 @@ int launch_resunit1_emul16(const jatts_resunit_desc& d, hipStream_t s) {
   if (KSPLIT && halo > 64) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit (single conv, emulated, channel halves): halo beyond 32 rows a side");
   const size_t region = resunit1_emul16_region<C, WGCOLS, KSPLIT>(halo);
   const size_t lds = region + C * sizeof(float);            // + b1
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit (single conv): tile exceeds 160 KiB LDS");
-  const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
-  dim3 grid((unsigned)((maxL + WGCOLS - 1) / WGCOLS), (unsigned)d.rg.n_seq);
-  if (const int64_t n1 = ragged_tiles_1d(d.rg, WGCOLS)) grid = dim3((unsigned)n1);
-  auto kern = resunit1_emul16_kernel<T, C, WGCOLS, WN, WT, OCC, KSPLIT, RREG>;
-  JATTS_RAISE_LDS_LIMIT(kern);
-  hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, (unsigned)region);
-  JATTS_CHECK_LAUNCH();
-  return JATTS_OK;
+  constexpr auto kern = resunit1_emul16_kernel<T, C, WGCOLS, WN, WT, OCC, KSPLIT, RREG>;
+  return unit_launch<kern>(JATTS_SITE("resunit (single conv): tile exceeds 160 KiB LDS"), WN * WT * 64, lds, WGCOLS, d.rg, s, d, (unsigned)region);
 }
 
 }  // namespace

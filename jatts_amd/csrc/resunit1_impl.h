@@ -24,6 +24,7 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC ? OCC : ((C <= 25
   const int K = d.k_w, dil = d.dil;
   const int p1 = (K - 1) / 2 * dil;
 
+  // unit_window_of (unit_frame.h), kept as this kernel's own copy: the helper's exits cost the smallest f16 tile 12 instructions, 1.06 % (profiles/r14_notes.md)
   int b = blockIdx.y, bx = blockIdx.x;
   if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, WGCOLS, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
   const int row_b = d.rg.cu_rows[b];
@@ -127,11 +128,7 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC ? OCC : ((C <= 25
   __syncthreads();
   {
     const int64_t g0 = (seq_row0 + t0) * (int64_t)C;  // the valid rows are contiguous in y: unit u <-> 8 elements at g0 + 8u
-    constexpr bool keep_small = C <= 64;   // small-channel kernels live on occupancy: keep the batch short
-    const T* xg = (const T*)d.x;
-    T* yg = (T*)d.y;
-    if (d.add0) unit_store_pass<T, C, keep_small ? 2 : 4, true, NTHR, !RREG>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);   // + fused MRF mean
-    else unit_store_pass<T, C, keep_small ? 4 : 8, false, NTHR, !RREG>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
+    unit_store<T, C, NTHR, !RREG>(d, ys, pitch, vrows, g0);
   }
 }
 
@@ -144,15 +141,8 @@ int launch_resunit1(const jatts_resunit_desc& d, hipStream_t s) {
   constexpr int WT = WGCOLS / (NT * 32);
   const int halo = (d.k_w - 1) / 2 * d.dil * 2;
   const size_t lds = resunit1_lds<T, C, WGCOLS>(halo);
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit (single conv): tile exceeds 160 KiB LDS");
-  const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
-  dim3 grid((unsigned)((maxL + WGCOLS - 1) / WGCOLS), (unsigned)d.rg.n_seq);
-  if (const int64_t n1 = ragged_tiles_1d(d.rg, WGCOLS)) grid = dim3((unsigned)n1);
-  auto kern = resunit1_kernel<T, C, WGCOLS, WN, NT, KCGMAX, OCC, RREG>;
-  JATTS_RAISE_LDS_LIMIT(kern);
-  hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, (unsigned)(lds - C * sizeof(float)));
-  JATTS_CHECK_LAUNCH();
-  return JATTS_OK;
+  constexpr auto kern = resunit1_kernel<T, C, WGCOLS, WN, NT, KCGMAX, OCC, RREG>;
+  return unit_launch<kern>(JATTS_SITE("resunit (single conv): tile exceeds 160 KiB LDS"), WN * WT * 64, lds, WGCOLS, d.rg, s, d, (unsigned)(lds - C * sizeof(float)));
 }
 
 }  // namespace

@@ -212,18 +212,9 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit_emul16_kernel(jatts_
   static_assert(!KSPLIT || KC32 % 2 == 0, "channel halves are whole K-steps");
   constexpr int MAXI = RREG ? (WGCOLS * (C / 8) + NTHR - 1) / NTHR : 1;      // interior units per thread (resunit_emul_impl.h: RREG)
   f32x8 xk[MAXI];
-  const unsigned wg_lin = blockIdx.x + blockIdx.y * gridDim.x;
-  const bool tracing = trace != nullptr && wg_lin < trace_cap && threadIdx.x == 0;
+  // phase stamps as in resunit_kernel (tools/trace_unit.py)
   // (SLIDE: the phase stamps are those of the run's last window)
-#define JATTS_STAMP(i) do { if (tracing) trace[(size_t)wg_lin * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-  if (tracing) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    trace[(size_t)wg_lin * 16] = ((unsigned long long)xcc << 32) | hwid;
-    trace[(size_t)wg_lin * 16 + 8] = __builtin_amdgcn_s_memrealtime();
-  }
-  JATTS_STAMP(1);
+  JATTS_TRACE_BEGIN(trace, trace_cap, blockIdx.x + blockIdx.y * gridDim.x);
   const int K = d.k_w, dil = d.dil;
   const int p2 = (K - 1) / 2, p1 = p2 * dil;
   const int tt_out = WGCOLS - 2 * p2;
@@ -231,6 +222,7 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit_emul16_kernel(jatts_
   int b, t0;                     // the window: sequence, first output position
   int64_t f_seq = 0, f_end = 0;  // SLIDE, in flat positions (rows past cu_rows[0] x len_mul): sequence b's first one, the end of this run
   if constexpr (!SLIDE) {
+    // the first half of unit_window_of (unit_frame.h), kept as this kernel's own copy: timed slower than the parent at some shapes with the helper (profiles/r14_notes.md)
     int bx = blockIdx.x;
     b = blockIdx.y;
     if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, tt_out, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
@@ -525,6 +517,7 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit_emul16_kernel(jatts_
           *reinterpret_cast<f32x4*>(dst + 4) = f32x4{o[4], o[5], o[6], o[7]};
         }
       } else {
+        // unit_store (unit_frame.h), kept as this kernel's own copy: timed slower than the parent at one shape with the helper (profiles/r14_notes.md)
         if (d.add0) unit_store_pass<float, C, keep_small ? 2 : 4, true, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
         else unit_store_pass<float, C, keep_small ? 4 : 8, false, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
       }
@@ -544,8 +537,7 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void resunit_emul16_kernel(jatts_
       break;
     }
   }
-  if (tracing) trace[(size_t)wg_lin * 16 + 9] = __builtin_amdgcn_s_memrealtime();
-#undef JATTS_STAMP
+  JATTS_TRACE_END();
 }
 
 // The form of a launch: 1 = windowed, 2 = sliding.  variant 0 (the library's choice): sliding when its runs -- one per resident workgroup, CUs x OCC --
@@ -569,7 +561,7 @@ int launch_resunit_emul16(const jatts_resunit_desc& d, hipStream_t s, int* pick)
   const size_t region = rows_x * pitch_x > rows_h * pitch ? rows_x * pitch_x : rows_h * pitch;
   const size_t tail = (size_t)(K - 1) * C * 6;                  // SLIDE: the parked h tail
   const size_t lds = region + 2 * C * sizeof(float);            // + b1 | b2
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: tile exceeds 160 KiB LDS");
+  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: tile exceeds 160 KiB LDS");   // (also what `pick` reports)
   int dev = 0, cus = 0;     // asked per launch: the device can differ from call to call
   hipError_t e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -582,20 +574,15 @@ int launch_resunit_emul16(const jatts_resunit_desc& d, hipStream_t s, int* pick)
     *pick = form;
     return JATTS_OK;
   }
-  if (form == 2) {
-    auto kern = resunit_emul16_kernel<T, C, WGCOLS, WN, WT, OCC, KSPLIT, RREG, true>;
-    JATTS_RAISE_LDS_LIMIT(kern);
+  if (form == 2) {      // one workgroup per run, not per window
+    constexpr auto kern = resunit_emul16_kernel<T, C, WGCOLS, WN, WT, OCC, KSPLIT, RREG, true>;
+    if (const int rc = unit_lds_ready<kern>(JATTS_SITE("resunit: tile exceeds 160 KiB LDS"), lds + tail)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)runs), dim3(WN * WT * 64), lds + tail, s, d, jatts_g_trace, jatts_g_trace_cap, (unsigned)(region + tail));
-  } else {
-    const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
-    dim3 grid((unsigned)((maxL + tt_out - 1) / tt_out), (unsigned)d.rg.n_seq);
-    if (const int64_t n1 = ragged_tiles_1d(d.rg, tt_out)) grid = dim3((unsigned)n1);
-    auto kern = resunit_emul16_kernel<T, C, WGCOLS, WN, WT, OCC, KSPLIT, RREG>;
-    JATTS_RAISE_LDS_LIMIT(kern);
-    hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, jatts_g_trace, jatts_g_trace_cap, (unsigned)region);
+    JATTS_CHECK_LAUNCH();
+    return JATTS_OK;
   }
-  JATTS_CHECK_LAUNCH();
-  return JATTS_OK;
+  constexpr auto kern = resunit_emul16_kernel<T, C, WGCOLS, WN, WT, OCC, KSPLIT, RREG>;
+  return unit_launch<kern>(JATTS_SITE("resunit: tile exceeds 160 KiB LDS"), WN * WT * 64, lds, tt_out, d.rg, s, d, jatts_g_trace, jatts_g_trace_cap, (unsigned)region);
 }
 
 }  // namespace

@@ -73,28 +73,16 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC) void resunit_emu
   static_assert(!(KSPLIT && RREG), "the residual registers go with the one-piece x tile");
   constexpr int MAXI = RREG ? (WGCOLS * (C / 8) + NTHR - 1) / NTHR : 1;      // interior units per thread
   f32x8 xk[MAXI];
-  const unsigned wg_lin = blockIdx.x + blockIdx.y * gridDim.x;
-  const bool tracing = trace != nullptr && wg_lin < trace_cap && threadIdx.x == 0;
-#define JATTS_STAMP(i) do { if (tracing) trace[(size_t)wg_lin * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-  if (tracing) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    trace[(size_t)wg_lin * 16] = ((unsigned long long)xcc << 32) | hwid;
-    trace[(size_t)wg_lin * 16 + 8] = __builtin_amdgcn_s_memrealtime();
-  }
-  JATTS_STAMP(1);
+  // phase stamps as in resunit_kernel (tools/trace_unit.py)
+  JATTS_TRACE_BEGIN(trace, trace_cap, blockIdx.x + blockIdx.y * gridDim.x);
   const int K = d.k_w, dil = d.dil;
   const int p2 = (K - 1) / 2, p1 = p2 * dil;
   const int tt_out = WGCOLS - 2 * p2;
 
-  int b = blockIdx.y, bx = blockIdx.x;
-  if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, tt_out, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
-  const int row_b = d.rg.cu_rows[b];
-  const int L = (d.rg.cu_rows[b + 1] - row_b) * d.rg.len_mul;
-  const int t0 = bx * tt_out;
-  if (t0 >= L) return;
-  const int64_t seq_row0 = (int64_t)row_b * d.rg.len_mul;
+  unit_window win;
+  if (!unit_window_of(d.rg, tt_out, win)) return;
+  const int L = win.L, t0 = win.t0;
+  const int64_t seq_row0 = win.seq_row0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wn = wave / WT, wt = wave % WT;
   const int g = lane >> 5;
@@ -313,10 +301,8 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC) void resunit_emu
   {
     const int vrows = min(tt_out, L - t0);
     const int64_t g0 = (seq_row0 + t0) * (int64_t)C;
-    constexpr bool keep_small = C <= 64;
-    const float* xg = (const float*)d.x;
-    float* yg = (float*)d.y;
     if constexpr (RREG) {
+      float* yg = (float*)d.y;
       // y = (acc + b2 tile in LDS) + x FROM REGISTERS [+ MRF partners] (unit_store_pass with the staged interior units)
       constexpr int UPR = C / 8;
       const int n_out = vrows * UPR;
@@ -349,13 +335,11 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC) void resunit_emu
         *reinterpret_cast<f32x4*>(dst + 4) = f32x4{o[4], o[5], o[6], o[7]};
       }
     } else {
-    if (d.add0) unit_store_pass<float, C, keep_small ? 2 : 4, true, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
-    else unit_store_pass<float, C, keep_small ? 4 : 8, false, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
+      unit_store<float, C, NTHR>(d, ys, pitch, vrows, g0);
     }
   }
   JATTS_STAMP(7);
-  if (tracing) trace[(size_t)wg_lin * 16 + 9] = __builtin_amdgcn_s_memrealtime();
-#undef JATTS_STAMP
+  JATTS_TRACE_END();
 }
 
 template <typename T, int C, int WGCOLS, int WN, int NT, int KCG = 2, int OCC = 2, bool KSPLIT = false, bool RREG = false>
@@ -370,15 +354,8 @@ int launch_resunit_emul(const jatts_resunit_desc& d, hipStream_t s) {
   size_t lds = rows_x * pitch_x > rows_h * pitch ? rows_x * pitch_x : rows_h * pitch;
   const unsigned bias_off = (unsigned)lds;
   lds += 2 * C * sizeof(float);                                // b1 | b2
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: tile exceeds 160 KiB LDS");
-  const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
-  dim3 grid((unsigned)((maxL + tt_out - 1) / tt_out), (unsigned)d.rg.n_seq);
-  if (const int64_t n1 = ragged_tiles_1d(d.rg, tt_out)) grid = dim3((unsigned)n1);
-  auto kern = resunit_emul_kernel<T, C, WGCOLS, WN, NT, KCG, OCC, KSPLIT, RREG>;
-  JATTS_RAISE_LDS_LIMIT(kern);
-  hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, jatts_g_trace, jatts_g_trace_cap, bias_off);
-  JATTS_CHECK_LAUNCH();
-  return JATTS_OK;
+  constexpr auto kern = resunit_emul_kernel<T, C, WGCOLS, WN, NT, KCG, OCC, KSPLIT, RREG>;
+  return unit_launch<kern>(JATTS_SITE("resunit: tile exceeds 160 KiB LDS"), WN * WT * 64, lds, tt_out, d.rg, s, d, jatts_g_trace, jatts_g_trace_cap, bias_off);
 }
 
 }  // namespace

@@ -1,61 +1,9 @@
 // Fused HiFi-GAN ResBlock dilation unit  y = x + conv_1(lrelu(conv_d(lrelu(x))))  (MFMA implicit GEMM, x and h tiles in LDS).
 // Instantiated per dtype / channel group in resunit_*.hip.
 #pragma once
-#include "conv_tiles.h"
-
-extern unsigned long long* jatts_g_trace;  // profiling hook (conv_api.hip: jatts_debug_trace)
-extern unsigned jatts_g_trace_cap;
+#include "unit_frame.h"
 
 namespace {
-
-// Unit-kernel output pass: y = (acc + b2 tile in LDS) + x [+ MRF partners] with row-contiguous 16-byte accesses;
-// all global reads of a batch are issued before any is consumed (one round trip per batch, not per unit).
-template <typename T, int C, int UB, bool ADD, int NTHR, bool RESID = true>
-__device__ __forceinline__ void unit_store_pass(const void* add0, const void* add1, float out_scale, const char* ys, int pitch,
-                                                int vrows, const T* xg, T* yg, int64_t g0) {
-  typedef typename Elem<T>::vec8 V8;
-  constexpr int UPR = C / 8;
-  const int total = vrows * UPR;
-  const bool has_add1 = ADD && add1 != nullptr;
-  for (int u0 = threadIdx.x; u0 < total; u0 += UB * NTHR) {
-    V8 xr[UB], a0[ADD ? UB : 1], a1[ADD ? UB : 1];
-#pragma unroll
-    for (int i = 0; i < UB; ++i) {
-      const int u = u0 + i * NTHR;
-      if (u < total) {
-        if (RESID && JATTS_ABLATE != 3) xr[i] = Vec8IO<T>::ldg(xg + g0 + (int64_t)u * 8);
-        if (ADD) {
-          a0[i] = Vec8IO<T>::ldg((const T*)add0 + g0 + (int64_t)u * 8);
-          if (has_add1) a1[i] = Vec8IO<T>::ldg((const T*)add1 + g0 + (int64_t)u * 8);
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < UB; ++i) {
-      const int u = u0 + i * NTHR;
-      if (u >= total) continue;
-      const int r = u / UPR, cu = u - r * UPR;
-      V8 v = Vec8IO<T>::lds(ys + (size_t)r * pitch + (size_t)cu * 8 * sizeof(T));
-      if (RESID && JATTS_ABLATE != 3) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = from_f32<T>(to_f32(v[e]) + to_f32(xr[i][e]));  // residual
-      }
-      if (ADD) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          v[e] = from_f32<T>((to_f32(v[e]) + to_f32(a0[i][e]) + (has_add1 ? to_f32(a1[i][e]) : 0.f)) * out_scale);
-      }
-      T* dst = yg + g0 + (int64_t)u * 8;
-      if ((JATTS_ABLATE != 4 && JATTS_ABLATE != 12) || to_f32(v[0]) == 12345.678f) {
-        if (sizeof(T) == 2) *reinterpret_cast<f16x8*>(dst) = *reinterpret_cast<const f16x8*>(&v);
-        else {
-          *reinterpret_cast<f32x4*>(dst) = f32x4{to_f32(v[0]), to_f32(v[1]), to_f32(v[2]), to_f32(v[3])};
-          *reinterpret_cast<f32x4*>(dst + 4) = f32x4{to_f32(v[4]), to_f32(v[5]), to_f32(v[6]), to_f32(v[7])};
-        }
-      }
-    }
-  }
-}
 
 __device__ __forceinline__ void lrelu8(f16x8& v, float slope) {
 #pragma unroll
@@ -125,23 +73,13 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC ? OCC : ((C <= 25
   constexpr int pitch = C * (int)sizeof(T) + 16;
   constexpr int KCG = sizeof(T) == 4 ? 2 : (KC16 < KCGMAX ? KC16 : KCGMAX);  // ring depth = group size
   static_assert(WT * NT * 32 == WGCOLS && NF * WN * 32 == C, "tile shape");
-  // Phase trace (profiling hook, jatts_debug_trace): thread 0 of the first trace_cap workgroups stamps s_memtime
-  // at every phase boundary: [hw id, start, staged, conv1, h written, conv2, y assembled, stored, realtime x2].
-  const unsigned wg_lin = blockIdx.x + blockIdx.y * gridDim.x;
-  const bool tracing = trace != nullptr && wg_lin < trace_cap && threadIdx.x == 0;
-#define JATTS_STAMP(i) do { if (tracing) trace[(size_t)wg_lin * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-  if (tracing) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    trace[(size_t)wg_lin * 16] = ((unsigned long long)xcc << 32) | hwid;
-    trace[(size_t)wg_lin * 16 + 8] = __builtin_amdgcn_s_memrealtime();
-  }
-  JATTS_STAMP(1);
+  // phase stamps: 1 start, 2 staged, 3 conv1, 10 .. 12 inside epilogue 1, 4 h written, 5 conv2, 6 y assembled, 7 stored (tools/trace_unit.py)
+  JATTS_TRACE_BEGIN(trace, trace_cap, blockIdx.x + blockIdx.y * gridDim.x);
   const int K = d.k_w, dil = d.dil;
   const int p2 = (K - 1) / 2, p1 = p2 * dil;
   const int tt_out = WGCOLS - 2 * p2;
 
+  // unit_window_of (unit_frame.h), kept as this kernel's own copy: timed slower than the parent at some shapes with the helper (profiles/r14_notes.md)
   int b = blockIdx.y, bx = blockIdx.x;
   if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, tt_out, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
   const int row_b = d.rg.cu_rows[b];
@@ -280,8 +218,6 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC ? OCC : ((C <= 25
   // is dead once every wave has left stage 2) and the residual is added in the row-contiguous 16-byte
   // store pass below: in MFMA fragment order both the x re-read and the y store scatter every 128-byte
   // line over 8 separate 8-byte accesses (1.4 ms of a 2.7 ms launch, profiles/r01_notes.md).
-  const T* xg = (const T*)d.x;
-  T* yg = (T*)d.y;
   if (JATTS_ABLATE == 8) return;
   __syncthreads();
   char* ys = smem;
@@ -320,13 +256,15 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC ? OCC : ((C <= 25
   {
     const int vrows = min(tt_out, L - t0);
     const int64_t g0 = (seq_row0 + t0) * (int64_t)C;  // the valid rows are contiguous in y: unit u <-> 8 elements at g0 + 8u
+    // unit_store (unit_frame.h), kept as this kernel's own copy: timed slower than the parent at some shapes with the helper (profiles/r14_notes.md)
     constexpr bool keep_small = C <= 64;   // small-channel kernels live on occupancy (6 workgroups/CU): keep the batch short
+    const T* xg = (const T*)d.x;
+    T* yg = (T*)d.y;
     if (d.add0) unit_store_pass<T, C, keep_small ? 2 : 4, true, WN * WT * 64, !RREG>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);   // + fused MRF mean
     else unit_store_pass<T, C, keep_small ? 4 : 8, false, WN * WT * 64, !RREG>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
   }
   JATTS_STAMP(7);
-  if (tracing) trace[(size_t)wg_lin * 16 + 9] = __builtin_amdgcn_s_memrealtime();
-#undef JATTS_STAMP
+  JATTS_TRACE_END();
 }
 
 template <typename T, int C, int WGCOLS, int WN, int NT, int KCGMAX = 8, int OCC = 0, bool RREG = false>
@@ -340,15 +278,8 @@ int launch_resunit(const jatts_resunit_desc& d, hipStream_t s) {
   size_t lds = (rows_x > rows_h ? rows_x : rows_h) * pitch;  // h overlays x
   const unsigned bias_off = (unsigned)lds;
   lds += 2 * C * sizeof(float);                               // b1 | b2
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: tile exceeds 160 KiB LDS");
-  const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
-  dim3 grid((unsigned)((maxL + tt_out - 1) / tt_out), (unsigned)d.rg.n_seq);
-  if (const int64_t n1 = ragged_tiles_1d(d.rg, tt_out)) grid = dim3((unsigned)n1);
-  auto kern = resunit_kernel<T, C, WGCOLS, WN, NT, KCGMAX, OCC, RREG>;
-  JATTS_RAISE_LDS_LIMIT(kern);
-  hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, jatts_g_trace, jatts_g_trace_cap, bias_off);
-  JATTS_CHECK_LAUNCH();
-  return JATTS_OK;
+  constexpr auto kern = resunit_kernel<T, C, WGCOLS, WN, NT, KCGMAX, OCC, RREG>;
+  return unit_launch<kern>(JATTS_SITE("resunit: tile exceeds 160 KiB LDS"), WN * WT * 64, lds, tt_out, d.rg, s, d, jatts_g_trace, jatts_g_trace_cap, bias_off);
 }
 
 }  // namespace

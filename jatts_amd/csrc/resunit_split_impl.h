@@ -59,21 +59,13 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC) void resunit_spl
   constexpr int pitch = C * 4 + 16;
   constexpr int NTHR = WN * WT * 64, NW = WN * WT;
   static_assert(WT * NT * 32 == WGCOLS && NF * WN * 32 == C, "tile shape");
-  const unsigned wg_lin = blockIdx.x + blockIdx.y * gridDim.x;
-  const bool tracing = trace != nullptr && wg_lin < trace_cap && threadIdx.x == 0;
-#define JATTS_STAMP(i) do { if (tracing) trace[(size_t)wg_lin * 16 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-  if (tracing) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    trace[(size_t)wg_lin * 16] = ((unsigned long long)xcc << 32) | hwid;
-    trace[(size_t)wg_lin * 16 + 8] = __builtin_amdgcn_s_memrealtime();
-  }
-  JATTS_STAMP(1);
+  // phase stamps as in resunit_kernel (tools/trace_unit.py)
+  JATTS_TRACE_BEGIN(trace, trace_cap, blockIdx.x + blockIdx.y * gridDim.x);
   const int K = d.k_w, dil = d.dil;
   const int p2 = (K - 1) / 2, p1 = p2 * dil;
   const int tt_out = WGCOLS - 2 * p2;
 
+  // unit_window_of (unit_frame.h), kept as this kernel's own copy: through the helper the two C = 256 tiles take one more register (profiles/r14_notes.md)
   int b = blockIdx.y, bx = blockIdx.x;
   if (ragged_is_1d(d.rg) && !ragged_locate(d.rg, tt_out, blockIdx.x, b, bx)) return;   // 1-D grid over the real tiles of a ragged batch
   const int row_b = d.rg.cu_rows[b];
@@ -241,15 +233,10 @@ __global__ __launch_bounds__(WN*(WGCOLS / (NT * 32)) * 64, OCC) void resunit_spl
   {
     const int vrows = min(tt_out, L - t0);
     const int64_t g0 = (seq_row0 + t0) * (int64_t)C;
-    constexpr bool keep_small = C <= 64;
-    const float* xg = (const float*)d.x;
-    float* yg = (float*)d.y;
-    if (d.add0) unit_store_pass<float, C, keep_small ? 2 : 4, true, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
-    else unit_store_pass<float, C, keep_small ? 4 : 8, false, NTHR>(d.add0, d.add1, d.out_scale, ys, pitch, vrows, xg, yg, g0);
+    unit_store<float, C, NTHR>(d, ys, pitch, vrows, g0);
   }
   JATTS_STAMP(7);
-  if (tracing) trace[(size_t)wg_lin * 16 + 9] = __builtin_amdgcn_s_memrealtime();
-#undef JATTS_STAMP
+  JATTS_TRACE_END();
 }
 
 template <int C, int WGCOLS, int WN, int NT, int KCG = 2, int OCC = 2>
@@ -264,15 +251,8 @@ int launch_resunit_split(const jatts_resunit_desc& d, hipStream_t s) {
   size_t lds = (rows_x > rows_h ? rows_x : rows_h) * pitch;
   const unsigned bias_off = (unsigned)lds;
   lds += 4 * C * sizeof(float) + 64;                           // b1 | b2 | 1/ws1 | 1/ws2 | amax slots
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "resunit: tile exceeds 160 KiB LDS");
-  const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
-  dim3 grid((unsigned)((maxL + tt_out - 1) / tt_out), (unsigned)d.rg.n_seq);
-  if (const int64_t n1 = ragged_tiles_1d(d.rg, tt_out)) grid = dim3((unsigned)n1);
-  auto kern = resunit_split_kernel<C, WGCOLS, WN, NT, KCG, OCC>;
-  JATTS_RAISE_LDS_LIMIT(kern);
-  hipLaunchKernelGGL(kern, grid, dim3(WN * WT * 64), lds, s, d, jatts_g_trace, jatts_g_trace_cap, bias_off);
-  JATTS_CHECK_LAUNCH();
-  return JATTS_OK;
+  constexpr auto kern = resunit_split_kernel<C, WGCOLS, WN, NT, KCG, OCC>;
+  return unit_launch<kern>(JATTS_SITE("resunit: tile exceeds 160 KiB LDS"), WN * WT * 64, lds, tt_out, d.rg, s, d, jatts_g_trace, jatts_g_trace_cap, bias_off);
 }
 
 }  // namespace

@@ -984,6 +984,87 @@ def test_ragged_1d_grids_equal_rectangular(cuda, lib, n_seq):
         assert torch.isfinite(a).all() and torch.equal(a, c)
 
 
+# Every kernel that decodes its window through csrc/unit_frame.h (unit_window_of): (name, dtype, w_layout, variant).  "unit" = the two-conv dilation unit,
+# "unit1" = the single-conv unit, "block" = the fused ResBlock; 7p / 6p = JATTS_F32E / JATTS_F32E6; w1 = w_layout 1 (16 x 16 x 32), v1 / v2 = windowed / sliding.
+_FRAMES = [("unit", "F32", 0, 0), ("unit", "F16", 0, 0), ("unit", "F32S", 0, 0), ("unit", "F32E", 0, 0), ("unit", "F32E6", 0, 0),
+           ("unit", "F32E", 1, 1), ("unit", "F32E", 1, 2), ("unit", "F32E6", 1, 1), ("unit", "F32E6", 1, 2),
+           ("unit1", "F32", 0, 0), ("unit1", "F16", 0, 0), ("unit1", "F32E", 1, 0), ("unit1", "F32E6", 1, 0),
+           ("block", "F32", 0, 0), ("block", "F16", 0, 0), ("block", "F32S", 0, 0), ("block", "F32E", 0, 0), ("block", "F32E6", 0, 0)]
+# one below, at and above W - (k - 1) and W for every window width W = 32 .. 512 the dispatchers use, plus the shortest sequences
+_FRAME_LENS_1 = [0, 1] + [w + i for w in (32, 64, 128, 256, 512) for i in (-3, -2, -1, 0, 1)]
+_FRAME_ALONE = (1, 254, 256, 513)      # sequences of batch 1 that are also launched alone
+_frame_cache = {}
+
+
+def _frame_data():
+    """Inputs shared by every case of the test below, made once and never written: batch 1 (the window edges), batch 2 (70 sequences: ragged_locate scans
+    a second block of 64), x ~ N(0, 1) for both, the weights of three units."""
+    if not _frame_cache:
+        g = torch.Generator().manual_seed(1405)
+        C, k = 32, 3
+        lens2 = [int(v) for v in torch.randint(0, 41, (68,), generator=g)] + [0, 600]
+        _frame_cache.update(
+            lens=(_FRAME_LENS_1, lens2), x=tuple(torch.randn(sum(ln), C, generator=g) for ln in (_FRAME_LENS_1, lens2)),
+            w=[(torch.randn(C, C, k, generator=g) / math.sqrt(C * k), torch.randn(C, generator=g) * 0.1,
+                torch.randn(C, C, k, generator=g) / math.sqrt(C * k), torch.randn(C, generator=g) * 0.1) for _ in range(3)])
+    return _frame_cache
+
+
+@pytest.mark.parametrize("form,mode,w_layout,variant", _FRAMES, ids=[f"{f}-{m}-w{wl}-v{v}" for f, m, wl, v in _FRAMES])
+def test_unit_window_frame_every_family(cuda, lib, form, mode, w_layout, variant):
+    """The window frame and launch rules shared by the nine fused-unit kernel families (csrc/unit_frame.h), in every family and arithmetic, at C = 32,
+    k = 3, dilation 3 (ResBlocks: 1, 3, 5), slope 0.1: (i) every output element is written and finite, (ii) the 1-D grid over the real windows of a
+    ragged batch equals the rectangular grid bit for bit, (iii) a sequence's rows do not depend on its batch (batch independence) -- a wrong
+    seq_row0 or L breaks that first.  Accuracy is the business of the per-family tests."""
+    from jatts_amd import hip
+    data = _frame_data()
+    C, k, dil, dils, slope = 32, 3, 3, (1, 3, 5), 0.1
+    dt = getattr(hip, mode)
+    tdt = hip.torch_dtype(dt)
+
+    def pack(w):
+        w = w.to(cuda)
+        if dt == hip.F32S:
+            return hip.pack_conv_weight_split(w, 32)
+        if dt in hip.EMUL:
+            return (hip.pack_unit_weight_bf16x3_k32(w) if w_layout == 1 else hip.pack_conv_weight_bf16x3(w, 32)), None
+        return hip.pack_conv_weight(w, dt, 32), None
+    units = [(pack(w1), b1.to(cuda), pack(w2), b2.to(cuda)) for w1, b1, w2, b2 in data["w"]]
+
+    def launch(lens, x):
+        rb = _ragged(lens, cuda)
+        y = torch.full_like(x, float("nan"))
+        (w1, i1), b1, (w2, i2), b2 = units[0]
+        if form == "unit":
+            hip.hifigan_resunit(rb, 1, x, y, w1, b1, w2, b2, C, k, dil, slope, dt, ws=(i1, i2) if dt == hip.F32S else None, w_layout=w_layout,
+                                variant=variant)
+        elif form == "unit1":
+            hip.hifigan_resunit(rb, 1, x, y, w1, b1, None, None, C, k, dil, slope, dt, w_layout=w_layout)
+        else:
+            hip.hifigan_resblock(rb, 1, x, y, [(u[0][0], u[1], u[2][0], u[3], d) for u, d in zip(units, dils)], C, k, slope, dt,
+                                 ws=[(u[0][1], u[2][1]) for u in units] if dt == hip.F32S else None)
+        torch.cuda.synchronize()
+        return y, rb
+
+    for batch, (lens, x) in enumerate(zip(data["lens"], data["x"])):
+        x = x.to(cuda).to(tdt)
+        one_d, rb = launch(lens, x)
+        assert rb.struct().host_lens, "a ragged batch takes the 1-D grid"
+        prev, hip._RAGGED_1D = hip._RAGGED_1D, False
+        try:
+            rect, rb = launch(lens, x)
+            assert not rb.struct().host_lens
+        finally:
+            hip._RAGGED_1D = prev
+        assert torch.isfinite(one_d.float()).all() and torch.isfinite(rect.float()).all(), f"batch {batch + 1}: unwritten / non-finite outputs"
+        assert torch.equal(one_d, rect), f"batch {batch + 1}: 1-D and rectangular grids differ"
+        if batch == 0:
+            for L in _FRAME_ALONE:
+                r0 = sum(lens[:lens.index(L)])
+                alone, _ = launch([L], x[r0:r0 + L].contiguous())
+                assert torch.equal(alone, one_d[r0:r0 + L]), f"sequence of length {L}: alone and inside the batch differ"
+
+
 @pytest.mark.parametrize("mode", ["F32", "F16", "F32S", "F32E", "F32E6"])
 @pytest.mark.parametrize("geom", [(384, 768, 384, [130, 1, 77, 768]), (512, 1024, 512, [300, 64]), (256, 256, 128, [40, 200, 5])],
                          ids=["fs2-384", "matcha-512", "small-256"])
