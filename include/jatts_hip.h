@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define JATTS_ABI_VERSION 7   /* (round 13: jatts_hifigan_resunit / jatts_resunit_variant take w2 == NULL as the single-conv dilation unit, without a bump: no descriptor or signature changed, and a library from before it lacks jatts_resunit_single_conv, so it is refused when _abi.load binds that symbol) (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
+#define JATTS_ABI_VERSION 7   /* (round 15 added jatts_stft_mag, jatts_logmel_post, jatts_energy_frames, jatts_energy_adjust and jatts_token_average without a bump, as rounds 10, 11 and 13 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 13: jatts_hifigan_resunit / jatts_resunit_variant take w2 == NULL as the single-conv dilation unit, without a bump: no descriptor or signature changed, and a library from before it lacks jatts_resunit_single_conv, so it is refused when _abi.load binds that symbol) (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
                                 * so every descriptor that embeds it (jatts_conv_desc, jatts_resunit_desc, jatts_resblock_desc, jatts_relattn_desc) shifted by 8 bytes; JATTS_F32E; 2 (round 4): jatts_conv_desc + w_inv / act_a / act_b, jatts_resunit_desc + ws1 / ws2, jatts_resblock_desc + ws1 / ws2;
                                 * bumped whenever a descriptor's layout or an entry point's signature changes: a stale library is refused at load */
 
@@ -666,6 +666,38 @@ int jatts_seq_affine_act(const jatts_ragged* rg, const float* x, int32_t ldx, in
 /* y[row*ldy + c] = x * sigmoid(s[b][c]) + resid (x, resid: [rows][dim]; resid may be NULL): SE gate + residual connection. */
 int jatts_se_scale_add(const jatts_ragged* rg, const float* x, int32_t dim, const float* s, const float* resid, float* y, int32_t ldy,
                        void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Stage-1 features of the recipes: log-mel filterbank (jatts/modules/feature_extract/mel.py:11-73) and
+ * frame / token energy (feature_extract/energy.py:69-122).  The reference computes both through librosa on the CPU; here the
+ * STFT is one exact-f32 MFMA contraction over raw samples, the mel projection a jatts_conv1d launch (k = 1, JATTS_F32), and
+ * the rest row-wise kernels.  All f32.  Every reduction is fixed-order (no atomics): a frame's bits depend on its own samples only.
+ * ------------------------------------------------------------------------------- */
+/* Magnitude STFT of packed waveforms (mel.py:44-52, energy.py:77-85: librosa.stft center=True, pad_mode="reflect", then np.abs):
+ *   mag[row(b,t)][k] = | sum_n x_b[refl(t*hop + n - n_fft/2)] * (table[n][k] + i table[n][nbp + k]) |,  k < n_bins = n_fft/2 + 1,
+ * columns n_bins..ldo-1 = 0.  refl is numpy's "reflect" (no edge repeat: -i -> i, L-1+i -> L-1-i).  table: [n_fft][2*nbp] f32 with
+ * nbp = n_bins rounded up to 32, column k = w[n] cos(2 pi n k / n_fft), column nbp + k = -w[n] sin(2 pi n k / n_fft), w the centred,
+ * zero-padded analysis window (jatts_amd.features.dft_table folds it in float64 and rounds once); padding columns are zero.
+ * rg_frames: utterance b has 1 + L_b / hop frames; cu_samples (device, n_seq+1) delimits the waveforms, host_samples (HOST, n_seq)
+ * repeats their lengths for the checks below (read at launch time only).  pow_sum (optional, [rows]): sum_k re^2 + im^2 per frame
+ * (energy.py:86-89), summed in a fixed order through the scratch of jatts_set_workspace (n_bin_tiles * rows floats).
+ * Neither the frame matrix nor the complex spectrum is written to memory.  JATTS_ERR_ARG: n_fft > 2048 or not a multiple of 64;
+ * hop < 1 or hop > n_fft; an utterance with L <= n_fft/2 (reflect would fold twice; torch.stft refuses it too); ldo < n_bins;
+ * rg_frames->max_len != max_b (1 + L_b / hop). */
+int jatts_stft_mag(const jatts_ragged* rg_frames, const int32_t* cu_samples, const int32_t* host_samples, const float* x,
+                   const float* table, int32_t n_fft, int32_t hop, float* mag, int32_t ldo, float* pow_sum, void* stream);
+/* out[row][c] = log_b(max(eps, mel[row][c])) for c < n_mels, 0 up to ldo (mel.py:64-73).  log_base: 0 = natural, 2 or 10. */
+int jatts_logmel_post(const float* mel, int32_t ldm, int32_t n_mels, int64_t rows, float eps, int32_t log_base, float* out,
+                      int32_t ldo, void* stream);
+/* e[row] = sqrt(max(pow_sum[row], 1e-10))  (energy.py:89) */
+int jatts_energy_frames(const float* pow_sum, int64_t rows, float* e, void* stream);
+/* _adjust_num_frames (energy.py:116-122) per utterance: out_b[t] = t < len_in_b ? e_b[t] : 0 for t < len_out_b (truncate or zero-pad). */
+int jatts_energy_adjust(const jatts_ragged* rg_in, const jatts_ragged* rg_out, const float* e, float* out, void* stream);
+/* _average_by_duration (energy.py:103-114): out[token] = mean of the strictly positive e over the token's span of frames, 0.0 when
+ * there are none (zero-duration tokens, spans of padded zeros).  cum (device int32, one per token): the inclusive scan of the
+ * durations inside each utterance = the end of the token's span; the caller has checked that they sum to the utterance's length. */
+int jatts_token_average(const jatts_ragged* rg_tokens, const jatts_ragged* rg_frames, const int32_t* cum, const float* e, float* out,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Length regulator (modules/length_regulator.py:70-97), bit-exact integer path.

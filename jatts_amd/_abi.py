@@ -137,6 +137,12 @@ PROTOTYPES = {
     "jatts_power_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     "jatts_fbank_post": (C.c_int, [C.POINTER(Ragged), C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p,
                                    C.c_int32, C.c_void_p]),
+    "jatts_stft_mag": (C.c_int, [C.POINTER(Ragged), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                 C.c_int32, C.c_void_p, C.c_void_p]),
+    "jatts_logmel_post": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "jatts_energy_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "jatts_energy_adjust": (C.c_int, [C.POINTER(Ragged), C.POINTER(Ragged), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jatts_token_average": (C.c_int, [C.POINTER(Ragged), C.POINTER(Ragged), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jatts_seq_mean_std": (C.c_int, [C.POINTER(Ragged), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "jatts_seq_affine_act": (C.c_int, [C.POINTER(Ragged), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,

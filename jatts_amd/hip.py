@@ -1273,6 +1273,70 @@ def se_scale_add(rb, x, s, resid=None, out=None, out_col0=0):
     return y
 
 
+# ---- stage-1 features (csrc/features.hip; host layer: jatts_amd/features.py)
+def stft_mag(rb_frames, cu_samples, n_samples, x, table, n_fft, hop, ldo, want_pow=False):
+    """jatts_stft_mag: packed f32 waveforms -> (mag f32 (rows, ldo), pow_sum f32 (rows,) or None).  ``n_samples``: host list of the
+    utterance lengths, ``cu_samples``: their exclusive scan on the device, ``table``: features.dft_table.  Geometry the library
+    refuses (n_fft, hop, ldo, short utterances) goes through to it for its message."""
+    lib = _abi.load()
+    x = _dev(x)
+    if x.dtype != torch.float32 or table.dtype != torch.float32 or not x.is_contiguous() or not table.is_contiguous():
+        raise ValueError("stft_mag: contiguous float32 samples and table expected")
+    if len(n_samples) != rb_frames.n_seq or cu_samples.numel() != rb_frames.n_seq + 1 or x.numel() < sum(n_samples):
+        raise ValueError("stft_mag: sample geometry does not match the frame geometry")
+    if 64 <= n_fft <= 2048 and table.numel() != n_fft * 2 * round_up(n_fft // 2 + 1, 32):
+        raise ValueError("stft_mag: table is not (n_fft, 2 * round_up(n_bins, 32))")
+    out = torch.empty(rb_frames.total, max(ldo, 1), dtype=torch.float32, device=x.device)
+    pw = torch.empty(rb_frames.total, dtype=torch.float32, device=x.device) if want_pow else None
+    ns = (C.c_int32 * len(n_samples))(*[int(v) for v in n_samples])
+    rg = rb_frames.struct()
+    if want_pow:
+        _ws(x.device)
+    rc = lib.jatts_stft_mag(C.byref(rg), _dev(cu_samples).data_ptr(), ns, x.data_ptr(), _dev(table).data_ptr(), n_fft, hop,
+                            out.data_ptr(), ldo, _ptr(pw), _stream())
+    if want_pow:
+        _ws_check(rc, "jatts_stft_mag")
+    else:
+        _abi.check(rc, "jatts_stft_mag")
+    _count(2.0 * n_fft * table.shape[-1] * rb_frames.total)
+    return out, pw
+
+
+def logmel_post(mel, n_mels, ldo, eps=1e-10, log_base=10):
+    """log_b(max(eps, mel)) with b = e (log_base 0), 2 or 10; columns n_mels .. ldo - 1 zero."""
+    lib = _abi.load()
+    out = torch.empty(mel.shape[0], ldo, dtype=torch.float32, device=mel.device)
+    _abi.check(lib.jatts_logmel_post(_dev(mel).data_ptr(), mel.shape[1], n_mels, mel.shape[0], eps, log_base, out.data_ptr(), ldo,
+                                     _stream()), "jatts_logmel_post")
+    return out
+
+
+def energy_frames(pow_sum):
+    lib = _abi.load()
+    e = torch.empty_like(pow_sum)
+    _abi.check(lib.jatts_energy_frames(_dev(pow_sum).data_ptr(), pow_sum.numel(), e.data_ptr(), _stream()), "jatts_energy_frames")
+    return e
+
+
+def energy_adjust(rb_in, rb_out, e):
+    """Per utterance truncate / zero-pad from rb_in's lengths to rb_out's."""
+    lib = _abi.load()
+    out = torch.empty(rb_out.total, dtype=torch.float32, device=e.device)
+    rgi, rgo = rb_in.struct(), rb_out.struct()
+    _abi.check(lib.jatts_energy_adjust(C.byref(rgi), C.byref(rgo), _dev(e).data_ptr(), out.data_ptr(), _stream()), "jatts_energy_adjust")
+    return out
+
+
+def token_average(rb_tokens, rb_frames, cum, e):
+    """Mean of the strictly positive frame values per token span; ``cum``: per-utterance inclusive scan of the durations (device int32)."""
+    lib = _abi.load()
+    out = torch.empty(rb_tokens.total, dtype=torch.float32, device=e.device)
+    rgt, rgf = rb_tokens.struct(), rb_frames.struct()
+    _abi.check(lib.jatts_token_average(C.byref(rgt), C.byref(rgf), _dev(cum).data_ptr(), _dev(e).data_ptr(), out.data_ptr(), _stream()),
+               "jatts_token_average")
+    return out
+
+
 # ---- training side (csrc/training.hip)
 def masked_loss(rb, a, b, valid_len, kind, scale, log_offset=-1.0):
     """scale * sum over valid rows of |a - b| (kind 0) or (a - b)^2 (kind 1); b -> log(b + log_offset) when log_offset >= 0."""
