@@ -700,6 +700,32 @@ int jatts_token_average(const jatts_ragged* rg_tokens, const jatts_ragged* rg_fr
                         void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Stage-1 statistics and normalisation (additive to ABI 7): the per-feature sklearn StandardScaler of
+ * jatts/bin/compute_statistics.py:75-103 (partial_fit per utterance, float64) as a running state on the device, and the
+ * StandardScaler.transform of jatts/datasets/tts_dataset.py:69-145.
+ * state: float64 [3][dim] = samples seen | mean | M2 (sum of squared deviations about the mean), all zero for an empty accumulator.
+ * ------------------------------------------------------------------------------- */
+#define JATTS_STATS_ROWS_PER_GROUP 1024
+/* The constant above, as compiled into the library. */
+int32_t jatts_stats_rows_per_group(void);
+/* One StandardScaler.partial_fit (compute_statistics.py:81-92) of x[rows][ld] f32, first `dim` columns (the others are never
+ * accumulated): state <- Chan / Golub / LeVeque pairwise update of state with the batch, accumulated in float64 in ONE pass about a
+ * shift (the running mean; the call's first row while the state is empty).  Fixed order: the rows are cut into groups of
+ * JATTS_STATS_ROWS_PER_GROUP, one workgroup per group and column tile stores its two sums to `ws` (device, the CALLER's, at least
+ * ceil(rows / JATTS_STATS_ROWS_PER_GROUP) * 2 * dim doubles, free again when the call has run; not the scratch of jatts_set_workspace), a second
+ * single-workgroup launch adds the groups in order and updates the state.  No atomics, no host synchronisation: the state's bits
+ * depend on the sequence of calls, their rows and dim only.  rows == 0: no-op.  NaN is NOT skipped (sklearn skips it).
+ * JATTS_ERR_ARG: dim < 1, ld < dim, rows < 0, a workspace too small. */
+int jatts_col_moments(const float* x, int32_t ld, int32_t dim, int64_t rows, double* state, double* ws, int64_t ws_doubles,
+                      void* stream);
+/* state <- state merged with other (the same pairwise update between two states: shards of one dataset); either may be empty. */
+int jatts_col_moments_merge(double* state, const double* other, int32_t dim, void* stream);
+/* StandardScaler.transform (tts_dataset.py:69-145): y[r][c] = (x[r][c] - mean[c]) / scale[c] for c < dim, one correctly rounded f32
+ * subtract and one correctly rounded f32 divide (no reciprocal); columns dim..ldy-1 = 0.  mean / scale: f32 [dim] on the device. */
+int jatts_standardize(const float* x, int32_t ldx, int32_t dim, int64_t rows, const float* mean, const float* scale, float* y,
+                      int32_t ldy, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Length regulator (modules/length_regulator.py:70-97), bit-exact integer path.
  * Step 1: d_eff = (alpha == 1) ? d : (int64) rint((float)d * alpha)   [half-to-even],
  *         cum[row] = inclusive prefix sum of d_eff inside each sequence, olens[b] = total.

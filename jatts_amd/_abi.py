@@ -15,6 +15,7 @@ ABI_VERSION = 7      # JATTS_ABI_VERSION of include/jatts_hip.h (tests/test_abi_
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SWISH, ACT_MISH, ACT_SNAKEBETA = 0, 1, 2, 3, 4, 5
 PRE_NONE, PRE_LRELU = 0, 1
 PAD_ZERO, PAD_REFLECT = 0, 1
+STATS_ROWS_PER_GROUP = 1024      # JATTS_STATS_ROWS_PER_GROUP (load() compares it with the library's)
 
 
 class Ragged(C.Structure):
@@ -143,6 +144,10 @@ PROTOTYPES = {
     "jatts_energy_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "jatts_energy_adjust": (C.c_int, [C.POINTER(Ragged), C.POINTER(Ragged), C.c_void_p, C.c_void_p, C.c_void_p]),
     "jatts_token_average": (C.c_int, [C.POINTER(Ragged), C.POINTER(Ragged), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jatts_stats_rows_per_group": (C.c_int32, []),
+    "jatts_col_moments": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "jatts_col_moments_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "jatts_standardize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "jatts_seq_mean_std": (C.c_int, [C.POINTER(Ragged), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "jatts_seq_affine_act": (C.c_int, [C.POINTER(Ragged), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
@@ -229,6 +234,8 @@ def load():
         fn.restype, fn.argtypes = res, args
     if lib.jatts_abi_version() != ABI_VERSION:
         raise JattsHipError(f"libjatts_hip.so ABI version {lib.jatts_abi_version()} != {ABI_VERSION} (include/jatts_hip.h): rebuild with __graft_entry__.build()")
+    if lib.jatts_stats_rows_per_group() != STATS_ROWS_PER_GROUP:
+        raise JattsHipError(f"libjatts_hip.so sums statistics in groups of {lib.jatts_stats_rows_per_group()} rows, _abi.py says {STATS_ROWS_PER_GROUP}: rebuild")
     _lib = lib
     return lib
 

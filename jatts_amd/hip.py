@@ -1337,6 +1337,53 @@ def token_average(rb_tokens, rb_frames, cum, e):
     return out
 
 
+# ---- stage-1 statistics (csrc/stats.hip; host layer: jatts_amd/features.py)
+def col_moments_ws_doubles(rows, dim):
+    """Doubles of workspace a col_moments call over ``rows`` rows needs: two sums per column and group of rows (include/jatts_hip.h)."""
+    return -(-int(rows) // _abi.STATS_ROWS_PER_GROUP) * 2 * int(dim) if rows > 0 else 0
+
+
+def col_moments(x, ld, dim, rows, state, ws):
+    """jatts_col_moments: one partial_fit of the f32 matrix x[rows][ld] (first ``dim`` columns) into ``state`` (float64 (3, dim):
+    n | mean | M2) through the caller's float64 workspace ``ws``.  Asynchronous, reads nothing back."""
+    lib = _abi.load()
+    x, state, ws = _dev(x), _dev(state), _dev(ws)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < rows * ld:
+        raise ValueError("col_moments: contiguous float32 (rows, ld) expected")
+    if state.dtype != torch.float64 or ws.dtype != torch.float64 or not state.is_contiguous() or state.numel() != 3 * dim:
+        raise ValueError("col_moments: state is float64 (3, dim), the workspace float64")
+    _abi.check(lib.jatts_col_moments(x.data_ptr(), ld, dim, rows, state.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "jatts_col_moments")
+    return state
+
+
+def col_moments_merge(state, other):
+    """state <- state merged with other (both float64 (3, dim))."""
+    lib = _abi.load()
+    state, other = _dev(state), _dev(other)
+    if state.dtype != torch.float64 or other.dtype != torch.float64 or state.shape != other.shape or state.dim() != 2 or state.shape[0] != 3:
+        raise ValueError("col_moments_merge: two float64 (3, dim) states expected")
+    if not state.is_contiguous() or not other.is_contiguous():
+        raise ValueError("col_moments_merge: contiguous states expected")
+    _abi.check(lib.jatts_col_moments_merge(state.data_ptr(), other.data_ptr(), state.shape[1], _stream()), "jatts_col_moments_merge")
+    return state
+
+
+def standardize(x, mean, scale, dim, ldy=None):
+    """jatts_standardize: (x - mean) / scale on the first ``dim`` columns of f32 x (rows, ld), zeros up to ``ldy`` (default: x's ld)."""
+    lib = _abi.load()
+    x, mean, scale = _dev(x), _dev(mean), _dev(scale)
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
+        raise ValueError("standardize: contiguous float32 (rows, ld) expected")
+    if mean.dtype != torch.float32 or scale.dtype != torch.float32 or mean.numel() < dim or scale.numel() < dim \
+            or not mean.is_contiguous() or not scale.is_contiguous():
+        raise ValueError("standardize: mean / scale are contiguous float32 with at least dim elements")
+    ldy = x.shape[1] if ldy is None else int(ldy)
+    y = torch.empty(x.shape[0], ldy, dtype=torch.float32, device=x.device)
+    _abi.check(lib.jatts_standardize(x.data_ptr(), x.shape[1], dim, x.shape[0], mean.data_ptr(), scale.data_ptr(), y.data_ptr(), ldy,
+                                     _stream()), "jatts_standardize")
+    return y
+
+
 # ---- training side (csrc/training.hip)
 def masked_loss(rb, a, b, valid_len, kind, scale, log_offset=-1.0):
     """scale * sum over valid rows of |a - b| (kind 0) or (a - b)^2 (kind 1); b -> log(b + log_offset) when log_offset >= 0."""
