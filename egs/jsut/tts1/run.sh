@@ -1,9 +1,10 @@
 #!/usr/bin/env bash
 # egs/jsut/tts1 on the MI355X path: the reference recipe's interface (same variables, same --option syntax, same directory
 # layout: exp/<expname>/{config.yml,stats.h5,tokens.txt,*.pkl} -> exp/<expname>/results/<checkpoint>/<set>/wav/*.wav) with
-# stage 4 (network decoding) running on jatts_amd.  Stages -1..3 (download, data preparation, feature extraction,
-# statistics, training) and 5 (evaluation) are the reference's and are not rebuilt here: run them there, then point
-# --expdir / --checkpoint at the result, or start this script with --stage 4 inside the reference's recipe directory.
+# stage 1 (feature extraction and statistics, egs/common/stage1.sh) and stage 4 (network decoding) running on jatts_amd.  Stages
+# -1, 0 (download, data preparation), 2, 3 (token list, training) and 5 (evaluation) are the reference's and are not rebuilt here:
+# run them there, then point --expdir / --checkpoint at the result, or start this script inside the reference's recipe directory.
+#     ./run.sh --stage 1 --stop_stage 1 [--conf conf/matcha_tts.mas.v1.yaml] [--dumpdir dump]
 #     ./run.sh --stage 4 --stop_stage 4 --tag mytag [--checkpoint exp/.../checkpoint-100000steps.pkl] [--n_gpus 8]
 
 log() {
@@ -25,6 +26,10 @@ n_gpus=1       # number of gpus (decoding: one process per GPU, utterances shard
 
 conf=conf/fastspeech2.v1.yaml
 
+# feature extraction related setting (stage 1)
+dumpdir=dump                # directory to dump full features
+preprocess_batch_size=32    # utterances per ragged batch
+
 # text related setting
 token_type="phn"
 token_column="phonemes"
@@ -45,6 +50,7 @@ master_port=29517
 
 # shellcheck disable=SC1091
 . "${REPO_ROOT}/egs/common/parse_options.sh" || exit 1
+. "${REPO_ROOT}/egs/common/stage1.sh" || exit 1
 . "${REPO_ROOT}/egs/common/stage4.sh" || exit 1
 
 set -euo pipefail
@@ -62,8 +68,17 @@ if [ -z "${expdir}" ]; then
     expdir=exp/${expname}
 fi
 
-if [ "${stage}" -le 3 ]; then
-    log "Stages <= 3 (data preparation, features, statistics, training) are the reference recipe's own: run them there."
+if [ "${stage}" -le 0 ]; then
+    log "Stages <= 0 (download, data preparation) are the reference recipe's own: run them there."
+fi
+
+if [ "${stage}" -le 1 ] && [ "${stop_stage}" -ge 1 ]; then
+    log "Stage 1: Feature extraction"
+    stage1_features
+fi
+
+if [ "${stage}" -le 3 ] && [ "${stop_stage}" -ge 2 ]; then
+    log "Stages 2 and 3 (token list generation, training) are the reference recipe's own: run them there."
 fi
 
 if [ "${stage}" -le 4 ] && [ "${stop_stage}" -ge 4 ]; then

@@ -700,6 +700,29 @@ int jatts_token_average(const jatts_ragged* rg_tokens, const jatts_ragged* rg_fr
                         void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Stage-1 audio reading (additive to ABI 7): the sample-rate conversion and the two amplitude checks of read_audio
+ * (jatts/utils/utils.py:201-234).  The reference resamples through librosa.load(sr=...) (soxr_hq); the converter here is a
+ * Kaiser-windowed-sinc polyphase FIR of this project's own definition (jatts_amd.features.resample_taps), pinned on
+ * scipy.signal.resample_poly.  Parity with librosa / soxr is UNPINNED.
+ * ------------------------------------------------------------------------------- */
+/* Rational resampling of packed waveforms by up / down (coprime; the taps h[0 .. 2*half_len] are folded into `table`):
+ *   y_b[m] = sum_n h[m*down - n*up + half_len] * x_b[n],  0 <= n < n_in_b, tap index in range, m < n_out_b = ceil(n_in_b * up / down),
+ * zeros beyond both ends: scipy.signal.resample_poly(x, up, down, window=h/up).  Computed as an exact-f32 MFMA contraction over
+ * blocks of Nb = up*r consecutive outputs (r = ceil(32/up) for up < 32, else 1), each advancing hop_b = down*r input samples:
+ *   Y[q][c] = sum_{i<K} x_b[q*hop_b - L + i] * table[i][c],  table[i][c] = h[c*down - (i - L)*up + half_len] or 0,  L = half_len / up,
+ *   K = ((Nb-1)*down + half_len) / up + L + 1 rounded up to 64; table: [K][Nbp] f32, Nbp = Nb rounded up to 32, padding columns zero
+ * (jatts_amd.features.resample_table).  The sum has a fixed order (a chain per 64 rows of the table, chains added in order; no atomics):
+ * an utterance's bits depend on its own samples and the table only.  Nothing is stored at or beyond n_out_b.
+ * cu_in / cu_out (device, n_seq+1) delimit the packed inputs / outputs; host_in (HOST, n_seq) repeats the input lengths for the
+ * checks (read at launch time only); table_rows must equal K.  JATTS_ERR_ARG: up, down or half_len < 1, table_rows != K, a negative
+ * length.  JATTS_ERR_UNSUPPORTED: K > 2048, Nbp > 512, more than 65535 utterances, 2^30 samples or more on either side. */
+int jatts_resample(int32_t n_seq, const int32_t* cu_in, const int32_t* cu_out, const int32_t* host_in, const float* x,
+                   const float* table, int32_t up, int32_t down, int32_t half_len, int32_t table_rows, float* y, void* stream);
+/* read_audio's checks and gain (utils.py:221-232) per utterance, in place: peak[2b] = max |y_b|, y_b *= gain (one f32 multiply),
+ * peak[2b+1] = max |y_b| afterwards (NaN propagates, as numpy's max does; 0 for an empty utterance).  cu: device, n_seq+1. */
+int jatts_wave_gain_peak(int32_t n_seq, const int32_t* cu, float* y, float gain, float* peak, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Stage-1 statistics and normalisation (additive to ABI 7): the per-feature sklearn StandardScaler of
  * jatts/bin/compute_statistics.py:75-103 (partial_fit per utterance, float64) as a running state on the device, and the
  * StandardScaler.transform of jatts/datasets/tts_dataset.py:69-145.

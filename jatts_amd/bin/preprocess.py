@@ -1,0 +1,198 @@
+"""Stage 1, first half: read the audio, resample it, extract and dump the raw features (the reference's ``jatts/bin/preprocess.py``)
+on the GPU.
+
+Same flags (``--csv --dumpdir --config [--f0_path] [--verbose]``, preprocess.py:39-66) plus ``--batch-size`` (utterances per ragged
+launch, default 32) and ``--dump-format`` (``npz``, the default and the pinned path, or ``h5`` where h5py is importable: unpinned).
+The config keys are the recipes': ``sampling_rate``, ``fft_size``, ``hop_size``, ``win_length``, ``window``, ``num_mels``, ``fmin``,
+``fmax``, ``global_gain_scale``, ``feat_list``, ``log_base``.
+
+Per batch the utterances are grouped by their files' native rate and every group is read -> ``jatts_resample`` ->
+``jatts_wave_gain_peak`` -> ``LogMelExtractor`` in batched, ragged launches (``features.read_audio_batch``).  ``energy`` runs through
+``features.Energy`` (the csv must carry ``durations``), ``spkemb`` through ``spkemb.SpkEmbExtractor`` with its "unverified" warning.
+``pitch`` (DIO needs pyworld) and the ``encodec*`` types (the encodec package) are refused with a NotImplementedError before any file
+is written; a ``--f0_path`` without ``pitch`` in the list is accepted and ignored.
+
+Every kept utterance becomes ``<dumpdir>/<sample_id>.npz`` (entries ``wave``, ``mel``, ... in float32: what
+``jatts_amd.bin.compute_statistics`` reads), written once, and the csv is rewritten with a ``feat_path`` column
+(preprocess.py:324-327).  An utterance whose gain clips is skipped with the reference's warning.
+
+The sample-rate conversion is pinned on scipy.signal.resample_poly; parity with the reference's librosa.load(sr=...) (soxr_hq) is
+UNPINNED, and so are the .h5 dumps.
+
+    python -m jatts_amd.bin.preprocess --csv data/train.csv --dumpdir dump/train/feats --config conf/matcha_tts.mas.v1.yaml
+"""
+import argparse
+import csv
+import logging
+import os
+
+import numpy as np
+import torch
+import yaml
+
+from jatts_amd import features
+
+_LOG_FORMAT = "%(asctime)s (%(module)s:%(lineno)d) %(levelname)s: %(message)s"
+_MISSING = {
+    "pitch": "feat_list holds 'pitch': the reference extracts it with DIO through pyworld, which is not installed here and has no "
+             "kernel in this package; remove 'pitch' from feat_list or run the reference's preprocess.py for this config",
+    "encodec": "feat_list holds '{}': EnCodec tokens need the encodec package, which is not installed here and has no kernel in this package",
+}
+_ENCODEC = ("encodec", "encodec_24khz", "encodec_48khz")
+
+
+def check_feat_list(config):
+    """The feature types this CLI serves, in the config's order.  Raises before anything is written: NotImplementedError for pitch and
+    encodec*, ValueError for the extractor types the reference refuses too (preprocess.py:122-150)."""
+    feats = list(config.get("feat_list", ["mel"]))
+    for f in feats + list(config.get("prompt_feat_list", [])):
+        if f == "pitch":
+            raise NotImplementedError(_MISSING["pitch"])
+        if f in _ENCODEC:
+            raise NotImplementedError(_MISSING["encodec"].format(f))
+    if "energy" in feats and config.get("energy_extract_type") != "energy":
+        raise ValueError(f"Unsupported energy extractor type: {config.get('energy_extract_type')}")
+    if "spkemb" in feats and config.get("spkemb_extract_type") != "speechbrain":
+        raise ValueError(f"Unsupported speaker embedding extractor type: {config.get('spkemb_extract_type')}")
+    if "spkemb" in feats and not spkemb_checkpoint(config):       # (the reference downloads it; as in jatts_amd.bin.tts_decode)
+        raise RuntimeError("feat_list has 'spkemb': set spkemb_checkpoint (config) or JATTS_SPKEMB_CHECKPOINT to SpeechBrain's ECAPA "
+                           "embedding_model.ckpt")
+    return feats
+
+
+def spkemb_checkpoint(config):
+    return config.get("spkemb_checkpoint") or os.environ.get("JATTS_SPKEMB_CHECKPOINT")
+
+
+def _h5_writer():
+    try:
+        import h5py
+    except ImportError as e:
+        raise ImportError("--dump-format h5 needs h5py; dump .npz (the default)") from e
+
+    def write(path, entries):
+        with h5py.File(path, "w") as f:
+            for k, v in entries.items():
+                f.create_dataset(k, data=v)
+    return write
+
+
+def _npz_writer():
+    def write(path, entries):
+        with open(path, "wb") as f:
+            np.savez(f, **entries)
+    return write
+
+
+def _none_if_empty(v):
+    return None if v is None or str(v).strip() == "" else v
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description="Preprocess audio and then extract features on the GPU (see jatts_amd/bin/preprocess.py).")
+    p.add_argument("--csv", required=True, type=str, help="csv file.")
+    p.add_argument("--dumpdir", type=str, required=True, help="directory to dump feature files.")
+    p.add_argument("--config", type=str, required=True, help="yaml format configuration file.")
+    p.add_argument("--f0_path", default=None, type=str, help="file storing f0 ranges (read only by pitch extraction, which is refused)")
+    p.add_argument("--verbose", type=int, default=1, help="logging level. higher is more logging. (default=1)")
+    p.add_argument("--batch-size", type=int, default=32, help="utterances per ragged launch (default=32)")
+    p.add_argument("--dump-format", choices=("npz", "h5"), default="npz", help="npz (default, pinned) or h5 (needs h5py; unpinned)")
+    args = p.parse_args(argv)
+    if args.verbose > 1:
+        logging.basicConfig(level=logging.DEBUG, format=_LOG_FORMAT)
+    elif args.verbose > 0:
+        logging.basicConfig(level=logging.INFO, format=_LOG_FORMAT)
+    else:
+        logging.basicConfig(level=logging.WARN, format=_LOG_FORMAT)
+        logging.warning("Skip DEBUG/INFO messages")
+    if args.batch_size < 1:
+        raise ValueError("--batch-size must be positive")
+
+    with open(args.config) as f:
+        config = yaml.load(f, Loader=yaml.Loader)
+    with open(args.csv, newline="") as f:
+        dataset = list(csv.DictReader(f))
+
+    # everything that can refuse does so here, before the first file is written
+    feats = check_feat_list(config)
+    known = [f for f in feats if f in ("mel", "energy", "spkemb")]
+    for f in feats:
+        if f not in known:
+            logging.info(f"Not supported feature type {f}. Skip.")
+    if "energy" in known and any(_none_if_empty(item.get("durations")) is None for item in dataset):
+        raise ValueError("feat_list holds 'energy': every row of the csv needs a durations column (token-averaged energy)")
+    write = _h5_writer() if args.dump_format == "h5" else _npz_writer()
+    if not dataset:
+        raise ValueError(f"{args.csv} lists no utterance")
+
+    device = torch.device("cuda")
+    sr = config["sampling_rate"]
+    stft = dict(fft_size=config["fft_size"], hop_size=config["hop_size"], win_length=config["win_length"], window=config["window"])
+    mel_ex = features.LogMelExtractor(device, sr, num_mels=config["num_mels"], fmin=config["fmin"], fmax=config["fmax"],
+                                      log_base=config.get("log_base", 10.0), **stft) if "mel" in known else None
+    energy_ex = None
+    if "energy" in known:
+        energy_ex = features.Energy(fs=sr, n_fft=config["fft_size"], win_length=config["win_length"], hop_length=config["hop_size"],
+                                    window=config["window"], use_token_averaged_energy=True,
+                                    reduction_factor=config["model_params"]["reduction_factor"], device=device)
+    spk_ex = None
+    if "spkemb" in known:
+        from jatts_amd.spkemb import SpkEmbExtractor
+        spk_ex = SpkEmbExtractor(device, checkpoint=spkemb_checkpoint(config), **config.get("spkemb_params", {}))       # ECAPA_TDNN kwargs
+
+    os.makedirs(args.dumpdir, exist_ok=True)
+    new_datas = []
+    for b0 in range(0, len(dataset), args.batch_size):
+        batch = dataset[b0:b0 + args.batch_size]
+        waves = features.read_audio_batch(
+            [(item["wav_path"], _none_if_empty(item.get("start")), _none_if_empty(item.get("end"))) for item in batch],
+            sr, config["global_gain_scale"], device)
+        kept = []
+        for item, w in zip(batch, waves):
+            if w is None:
+                logging.warning(f"{item['wav_path']} returns None. Skip.")
+            else:
+                kept.append((item, w))
+        if not kept:
+            continue
+        durations = None
+        if _none_if_empty(kept[0][0].get("durations")) is not None:
+            durations = [None if _none_if_empty(item.get("durations")) is None else [int(d) for d in item["durations"].split(" ")]
+                         for item, _ in kept]
+        pw = features.PackedWaves(torch.cat([w for _, w in kept]).contiguous(), [int(w.numel()) for _, w in kept])
+        entries = [{"wave": w.cpu().numpy().astype(np.float32)} for _, w in kept]
+        if mel_ex is not None:
+            rb, mel = mel_ex(pw)
+            mel = mel[:, :mel_ex.num_mels].cpu().numpy()
+            for i, (item, _) in enumerate(kept):
+                feat = mel[rb.cu_host[i]:rb.cu_host[i + 1]]
+                if durations is not None and durations[i] is not None:      # check duration (preprocess.py:258-261)
+                    total = sum(durations[i])
+                    assert total == feat.shape[0], \
+                        f"{item['sample_id']}: mel duration {feat.shape[0]} and phoneme durations {total} don't match ."
+                entries[i]["mel"] = np.ascontiguousarray(feat, dtype=np.float32)
+        if energy_ex is not None:
+            en = energy_ex._ex.energy(pw, [sum(d) for d in durations], durations)
+            for i, e in enumerate(en):
+                entries[i]["energy"] = e.cpu().numpy().astype(np.float32)
+        if spk_ex is not None:
+            emb = spk_ex.forward_many([item["wav_path"] for item, _ in kept])
+            for i in range(len(kept)):
+                entries[i]["spkemb"] = np.asarray(emb[i], dtype=np.float32).reshape(-1)
+        for (item, _), ent in zip(kept, entries):
+            feat_path = os.path.join(args.dumpdir, f"{item['sample_id']}.{args.dump_format}")
+            write(feat_path, ent)
+            new_datas.append({**item, "feat_path": os.path.realpath(feat_path)})
+        logging.info("%d / %d utterances done", min(b0 + args.batch_size, len(dataset)), len(dataset))
+
+    if not new_datas:
+        raise ValueError(f"no utterance of {args.csv} was kept")
+    with open(args.csv, "w", newline="") as f:                               # write_csv (utils.py:87-100)
+        writer = csv.DictWriter(f, fieldnames=list(new_datas[0].keys()))
+        writer.writeheader()
+        for line in new_datas:
+            writer.writerow(line)
+
+
+if __name__ == "__main__":
+    main()

@@ -17,6 +17,12 @@ The second half of stage 1 lives here too: ``FeatureStatistics`` is the per-feat
 ``partial_fit``, fixed summation order, no read-back before ``finalize``), ``standardize`` the ``StandardScaler.transform`` of
 ``jatts/datasets/tts_dataset.py:69-145`` (``jatts_standardize``).  These ARE pinned on the real thing: sklearn 1.7.2 wrote
 ``tests/golden/stats_kat.npz``.  ``python -m jatts_amd.bin.compute_statistics`` is the reference's CLI on top of them.
+
+The first step of stage 1 is here as well: ``read_audio`` (``jatts/utils/utils.py:201-234``) with its sample-rate conversion as a
+kernel (``Resampler`` / ``resample``, ``jatts_resample``: a Kaiser-windowed-sinc polyphase FIR of our own definition, an exact-f32
+MFMA contraction like the STFT).  The converter is pinned exactly on ``scipy.signal.resample_poly`` in float64
+(``tests/golden/resample_kat.npz``); parity with ``librosa.load(sr=...)``, whose default is soxr_hq, is UNPINNED.
+``python -m jatts_amd.bin.preprocess`` is the reference's stage-1 CLI on top of all of it.
 """
 import functools
 import math
@@ -145,6 +151,12 @@ class LogMelExtractor:
         self.mel_w = hip.pack_conv_weight(torch.from_numpy(mel.T.copy()).float().unsqueeze(-1).to(self.device), F32, 64)
 
     def _stft(self, waves, want_pow):
+        if isinstance(waves, PackedWaves):                          # already packed on the device (Resampler's output): no copy
+            if not waves.lens:
+                raise ValueError("no waveform")
+            rb = hip.RaggedBatch([frame_count(n, self.n_fft, self.hop) for n in waves.lens], self.device)
+            mag, pw = hip.stft_mag(rb, waves.cu, waves.lens, waves.x, self.table, self.n_fft, self.hop, self.ld_mag, want_pow=want_pow)
+            return rb, mag, pw
         ws = [torch.as_tensor(w).reshape(-1) for w in waves]
         if not ws:
             raise ValueError("no waveform")
@@ -375,3 +387,250 @@ def standardize(x, mean, scale, dim=None):
         raise ValueError(f"standardize: float32 (rows, ld >= {dim}) expected, got {x.dtype} {tuple(x.shape)}")
     y = hip.standardize(x2.contiguous(), m.to(x.device).contiguous(), s.to(x.device).contiguous(), dim)
     return y.reshape(-1) if x.dim() == 1 else y
+
+
+# ---- sample-rate conversion and read_audio (csrc/resample.hip)
+# The converter is this project's own: a Kaiser-windowed-sinc polyphase FIR.  Its arithmetic is pinned exactly on
+# scipy.signal.resample_poly in float64 (tests/golden/resample_kat.npz).  Parity with librosa.load(sr=...), whose default is soxr_hq,
+# is UNPINNED: librosa, soxr and resampy are absent from the build environment.
+RESAMPLE_ZEROS = 64                          # zero crossings of the sinc a side, per unit of max(up, down)
+RESAMPLE_ROLLOFF = 0.9475937167399596        # cutoff as a share of the lower Nyquist  } the published "kaiser_best" constants [recalled,
+RESAMPLE_BETA = 14.769656459379492           # Kaiser window parameter                 } not verifiable here]
+RESAMPLE_MAX_K, RESAMPLE_MAX_NBP, RESAMPLE_MAX_TABLE_BYTES = 2048, 512, 4 << 20
+
+
+def resample_ratio(sr_in, sr_out):
+    """(up, down) in lowest terms for integer sampling rates."""
+    if int(sr_in) != sr_in or int(sr_out) != sr_out or sr_in < 1 or sr_out < 1:
+        raise ValueError(f"sampling rates must be positive integers (got {sr_in} -> {sr_out})")
+    g = math.gcd(int(sr_in), int(sr_out))
+    return int(sr_out) // g, int(sr_in) // g
+
+
+def resample_taps(sr_in, sr_out, zeros=RESAMPLE_ZEROS, rolloff=RESAMPLE_ROLLOFF, beta=RESAMPLE_BETA):
+    """float32 (2 * half_len + 1,), half_len = zeros * max(up, down): up * firwin(2 * half_len + 1, rolloff / max(up, down),
+    window=("kaiser", beta)), restated from the formula -- sinc low-pass times the symmetric Kaiser window (np.i0), scaled to unit gain
+    at DC -- designed in float64 and rounded ONCE.  zeros=10, rolloff=1, beta=5 is scipy.signal.resample_poly's own default design
+    (-14 dB just above the Nyquist frequency: not ours)."""
+    return resample_design(sr_in, sr_out, zeros, rolloff, beta).astype(np.float32)
+
+
+def resample_design(sr_in, sr_out, zeros=RESAMPLE_ZEROS, rolloff=RESAMPLE_ROLLOFF, beta=RESAMPLE_BETA):
+    """The float64 design ``resample_taps`` rounds."""
+    up, down = resample_ratio(sr_in, sr_out)
+    m_rate = max(up, down)
+    zeros = int(zeros)
+    if up == down or zeros < 1 or not 0.0 < rolloff / m_rate < 1.0 or beta < 0.0:
+        raise ValueError(f"no filter for {sr_in} -> {sr_out} with zeros={zeros}, rolloff={rolloff}, beta={beta}")
+    half_len = zeros * m_rate
+    m = np.arange(-half_len, half_len + 1, dtype=np.float64)
+    cutoff = float(rolloff) / m_rate
+    h = cutoff * np.sinc(cutoff * m)
+    h *= np.i0(float(beta) * np.sqrt(1.0 - (m / half_len) ** 2)) / np.i0(float(beta))
+    h /= h.sum()
+    return up * h
+
+
+def resample_out_len(n_in, up, down):
+    """ceil(n_in * up / down)"""
+    return -(-int(n_in) * up // down)
+
+
+def resample_geometry(up, down, half_len):
+    """The block form the kernel runs (include/jatts_hip.h: jatts_resample) -> dict r, Nb, Nbp, hop_b, L, K.  A block is Nb = up * r
+    consecutive outputs (r = ceil(32 / up) for up < 32, else 1), so every block meets the taps in the same phase pattern, and advances
+    hop_b = down * r input samples; L = half_len // up input samples precede its first output's centre; K input samples feed it."""
+    r = -(-32 // up) if up < 32 else 1
+    nb, hop_b, lead = up * r, down * r, half_len // up
+    k = hip.round_up(((nb - 1) * down + half_len) // up + lead + 1, 64)
+    return dict(r=r, Nb=nb, Nbp=hip.round_up(nb, 32), hop_b=hop_b, L=lead, K=k)
+
+
+def resample_table(taps, up, down):
+    """float32 (K, Nbp): W[i][c] = taps[c * down - (i - L) * up + half_len] where that index is in range and c < Nb, else 0 -- pure
+    indexing of the f32 taps, no arithmetic.  ValueError beyond the kernel's limits."""
+    taps = np.asarray(taps, dtype=np.float32)
+    if taps.ndim != 1 or taps.size % 2 != 1 or taps.size < 3:
+        raise ValueError("taps: an odd number (2 * half_len + 1) expected")
+    half_len = taps.size // 2
+    g = resample_geometry(up, down, half_len)
+    if g["K"] > RESAMPLE_MAX_K:
+        raise ValueError(f"resampling {up}/{down} with {taps.size} taps needs K = {g['K']} input samples per block: the limit is K <= {RESAMPLE_MAX_K}")
+    if g["Nbp"] > RESAMPLE_MAX_NBP:
+        raise ValueError(f"resampling {up}/{down} needs Nbp = {g['Nbp']} table columns: the limit is Nbp <= {RESAMPLE_MAX_NBP}")
+    if g["K"] * g["Nbp"] * 4 > RESAMPLE_MAX_TABLE_BYTES:
+        raise ValueError(f"resampling {up}/{down} needs a table of {g['K'] * g['Nbp'] * 4} bytes: the limit is {RESAMPLE_MAX_TABLE_BYTES} bytes (4 MiB)")
+    i = np.arange(g["K"], dtype=np.int64)[:, None]
+    c = np.arange(g["Nbp"], dtype=np.int64)[None, :]
+    j = c * down - (i - g["L"]) * up + half_len
+    ok = (j >= 0) & (j < taps.size) & (c < g["Nb"])
+    return np.where(ok, taps[np.clip(j, 0, taps.size - 1)], np.float32(0.0)).astype(np.float32)
+
+
+def seconds_to_samples(start, end, sr_native):
+    """read_audio's ``start`` / ``end`` (seconds; utils.py:204-209: offset = start, duration = end - start) -> (first sample, number of
+    samples) at the file's own rate, both by truncation: int(offset * sr), int(duration * sr), what librosa.load does [recalled].
+    Either being None reads the whole file: (0, None)."""
+    if start is None or end is None:
+        return 0, None
+    offset, duration = float(start), float(end) - float(start)
+    if offset < 0.0 or duration < 0.0:
+        raise ValueError(f"start {start} / end {end}: a non-negative offset and duration expected")
+    return int(offset * sr_native), int(duration * sr_native)
+
+
+class PackedWaves:
+    """A ragged batch of waveforms in one device buffer: ``x`` f32 (sum(lens),), ``lens`` on the host, ``cu`` their exclusive scan on the
+    device.  What ``Resampler`` returns for such an input and ``LogMelExtractor`` consumes without a copy."""
+
+    def __init__(self, x, lens):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise _abi.JattsHipError("jatts_amd.features runs on the GPU only (no CPU fallback): PackedWaves takes a device tensor")
+        self.lens = [int(v) for v in lens]
+        if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous() or x.numel() != sum(self.lens) or min(self.lens, default=0) < 0:
+            raise ValueError("PackedWaves: a contiguous 1-D float32 buffer of sum(lens) samples expected")
+        self.x = x
+        self.cu_host = [0]
+        for n in self.lens:
+            self.cu_host.append(self.cu_host[-1] + n)
+        self.cu = hip.h2d(self.cu_host, torch.int32, x.device)
+
+    @classmethod
+    def from_list(cls, waves, device):
+        ws = [torch.as_tensor(w).reshape(-1).to(torch.float32) for w in waves]
+        return cls(torch.cat(ws).to(device).contiguous(), [int(w.numel()) for w in ws])
+
+    def split(self):
+        """list of per-utterance views of ``x``"""
+        return [self.x[a:b] for a, b in zip(self.cu_host[:-1], self.cu_host[1:])]
+
+
+class Resampler:
+    """Rational sample-rate conversion sr_in -> sr_out on the GPU (``jatts_resample``), taps and table cached on the device.
+
+    ``resampler(waves)``: a list of 1-D float32 DEVICE tensors -> a list of device tensors (views of one buffer), or a ``PackedWaves``
+    -> a ``PackedWaves``; utterance b has ceil(n_b * up / down) samples.  sr_in == sr_out returns the input untouched.  The result is
+    bit for bit independent of how the utterances are batched.  Pinned on scipy.signal.resample_poly with these taps; parity with
+    librosa.load(sr=...) (soxr_hq) is UNPINNED."""
+
+    def __init__(self, device, sr_in, sr_out, zeros=RESAMPLE_ZEROS, rolloff=RESAMPLE_ROLLOFF, beta=RESAMPLE_BETA):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _abi.JattsHipError("jatts_amd.features runs on the GPU only (no CPU fallback)")
+        self.sr_in, self.sr_out = int(sr_in), int(sr_out)
+        self.up, self.down = resample_ratio(sr_in, sr_out)
+        self.identity = self.up == self.down
+        if self.identity:
+            return
+        taps = resample_taps(sr_in, sr_out, zeros, rolloff, beta)
+        self.half_len = taps.size // 2
+        self.geometry = resample_geometry(self.up, self.down, self.half_len)
+        table = resample_table(taps, self.up, self.down)
+        _abi.load()
+        self.taps = torch.from_numpy(taps).to(self.device)
+        self.table = torch.from_numpy(table).to(self.device)
+
+    def out_len(self, n_in):
+        return int(n_in) if self.identity else resample_out_len(n_in, self.up, self.down)
+
+    @torch.no_grad()
+    def packed(self, pw):
+        if not isinstance(pw, PackedWaves):
+            raise TypeError("Resampler.packed takes a PackedWaves")
+        if self.identity:
+            return pw
+        n_out = [self.out_len(n) for n in pw.lens]
+        cu_out = [0]
+        for n in n_out:
+            cu_out.append(cu_out[-1] + n)
+        y = hip.resample(pw.cu, hip.h2d(cu_out, torch.int32, pw.x.device), pw.lens, n_out, pw.x, self.table, self.up, self.down,
+                         self.half_len)
+        return PackedWaves(y, n_out)
+
+    def __call__(self, waves):
+        if isinstance(waves, PackedWaves):
+            return self.packed(waves)
+        waves = list(waves)
+        for w in waves:
+            if not isinstance(w, torch.Tensor) or not w.is_cuda:
+                raise _abi.JattsHipError("jatts_amd.features runs on the GPU only (no CPU fallback): Resampler takes device tensors")
+            if w.dtype != torch.float32 or w.dim() != 1:
+                raise ValueError(f"Resampler: 1-D float32 waveforms expected, got {w.dtype} {tuple(w.shape)}")
+        if self.identity or not waves:
+            return waves
+        return self.packed(PackedWaves(torch.cat(waves).contiguous(), [int(w.numel()) for w in waves])).split()
+
+
+@functools.lru_cache(maxsize=16)
+def _resampler(device, sr_in, sr_out, zeros, rolloff, beta):
+    return Resampler(device, sr_in, sr_out, zeros, rolloff, beta)
+
+
+def resample(x, sr_in, sr_out, zeros=RESAMPLE_ZEROS, rolloff=RESAMPLE_ROLLOFF, beta=RESAMPLE_BETA):
+    """One-shot form: a 1-D float32 device tensor (or a list of them, or a ``PackedWaves``) at sr_in -> the same at sr_out.  One
+    ``Resampler`` is kept per device and parameter set."""
+    one = isinstance(x, torch.Tensor)
+    first = x if one else (x.x if isinstance(x, PackedWaves) else (x[0] if len(x) else None))
+    if first is not None and (not isinstance(first, torch.Tensor) or not first.is_cuda):
+        raise _abi.JattsHipError("jatts_amd.features runs on the GPU only (no CPU fallback): resample takes device tensors")
+    if first is None:
+        return []
+    rs = _resampler(str(first.device), int(sr_in), int(sr_out), int(zeros), float(rolloff), float(beta))
+    return rs([x])[0] if one else rs(x)
+
+
+_NOT_PCM = "{} seems to be different from 16 bit PCM."                       # utils.py:223
+_CLIPPING = "{} causes clipping (max: {}). it is better to re-consider global gain scale."      # utils.py:229-230
+
+
+def read_audio_batch(items, sr, global_gain_scale=1.0, device="cuda"):
+    """``read_audio`` for a batch: ``items`` = (wav_path, start, end) per utterance -> a list with, per utterance, a 1-D float32 device
+    tensor at ``sr`` or None where the gain clips (the reference's warning is logged).  Files are decoded on the host, grouped by their
+    native rate, and each group is ONE upload, ONE ``jatts_resample`` launch and ONE ``jatts_wave_gain_peak`` launch; the peaks of the
+    whole batch come back in one read."""
+    import logging
+
+    from .wavio import decode_wav
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _abi.JattsHipError("jatts_amd.features runs on the GPU only (no CPU fallback)")
+    groups = {}
+    for idx, (path, start, end) in enumerate(items):
+        a, rate = decode_wav(path)
+        a = a[:, 0] if a.shape[1] == 1 else a.mean(axis=1, dtype=np.float32)          # mono=True: the channels' mean [recalled]
+        first, count = seconds_to_samples(start, end, rate)
+        a = a[first:] if count is None else a[first:first + count]
+        if a.size == 0:
+            raise ValueError(f"{path}: no samples between start {start} and end {end}")
+        groups.setdefault(rate, []).append((idx, np.ascontiguousarray(a, dtype=np.float32)))
+    out, runs = [None] * len(items), []
+    for rate, members in groups.items():
+        pw = PackedWaves(torch.from_numpy(np.concatenate([a for _, a in members])).pin_memory().to(dev, non_blocking=True),
+                         [a.size for _, a in members])
+        rs = _resampler(str(dev), int(rate), int(sr), RESAMPLE_ZEROS, RESAMPLE_ROLLOFF, RESAMPLE_BETA)
+        pw = rs.packed(pw)
+        runs.append((members, pw, hip.wave_gain_peak(pw.cu, len(members), pw.x, global_gain_scale)))
+    for members, pw, peak in runs:
+        peak = peak.cpu().numpy()
+        for (idx, _), w, (before, after) in zip(members, pw.split(), peak):
+            path = items[idx][0]
+            if not before <= 1.0:
+                raise AssertionError(_NOT_PCM.format(path))
+            if not after <= 1.0:
+                logging.warning(_CLIPPING.format(path, after))
+                continue
+            out[idx] = w
+    return out
+
+
+def read_audio(wav_path, sr, start=None, end=None, global_gain_scale=1.0):
+    """The reference's ``read_audio`` (jatts/utils/utils.py:201-234), computed on cuda (the current device): the file between ``start``
+    and ``end`` (seconds; both or neither) at ``sr``, times ``global_gain_scale`` -> float32 ndarray, or None (with the reference's
+    warning) when the gain clips.  A peak above 1 before the gain raises AssertionError in the reference's words.
+
+    The file is decoded as integer PCM (``wavio.decode_wav``); the sample-rate conversion is ``Resampler``'s -- pinned on
+    scipy.signal.resample_poly, parity with librosa.load(sr=...) (soxr_hq) UNPINNED.  Two facts about librosa.load are [recalled],
+    not verifiable here: a multi-channel file is reduced to the mean of its channels (mono=True), and ``start`` / ``end`` become sample
+    offsets at the file's own rate by truncation (int(offset * sr_native), int(duration * sr_native))."""
+    w = read_audio_batch([(wav_path, start, end)], sr, global_gain_scale)[0]
+    return None if w is None else w.cpu().numpy()

@@ -1337,6 +1337,47 @@ def token_average(rb_tokens, rb_frames, cum, e):
     return out
 
 
+# ---- stage-1 audio reading (csrc/resample.hip; host layer: jatts_amd/features.py)
+def resample(cu_in, cu_out, n_in, n_out, x, table, up, down, half_len, out=None):
+    """jatts_resample: packed f32 waveforms -> packed f32 waveforms at up / down times the rate.  ``n_in`` / ``n_out``: host lists of the
+    utterance lengths (n_out = ceil(n_in * up / down)), ``cu_in`` / ``cu_out``: their exclusive scans on the device, ``table``:
+    features.resample_table (K, Nbp).  ``out``: a device buffer of at least sum(n_out) floats to write into (default: a new one)."""
+    lib = _abi.load()
+    x, table = _dev(x), _dev(table)
+    if x.dtype != torch.float32 or table.dtype != torch.float32 or not x.is_contiguous() or not table.is_contiguous() or table.dim() != 2:
+        raise ValueError("resample: contiguous float32 samples and a (K, Nbp) float32 table expected")
+    n_in, n_out = [int(v) for v in n_in], [int(v) for v in n_out]
+    if len(n_out) != len(n_in) or cu_in.numel() != len(n_in) + 1 or cu_out.numel() != len(n_in) + 1 or x.numel() < sum(n_in):
+        raise ValueError("resample: sample geometry does not match the lengths")
+    if any(o != -(-n * up // down) for n, o in zip(n_in, n_out)):
+        raise ValueError("resample: n_out is not ceil(n_in * up / down)")
+    nb = up * (-(-32 // up) if up < 32 else 1)
+    if table.shape[1] != round_up(nb, 32):
+        raise ValueError("resample: table is not (K, round_up(up * r, 32))")
+    total = sum(n_out)
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=x.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < total:
+        raise ValueError("resample: out must be a contiguous float32 device buffer of at least sum(n_out) elements")
+    ns = (C.c_int32 * max(len(n_in), 1))(*n_in)
+    _abi.check(lib.jatts_resample(len(n_in), _dev(cu_in).data_ptr(), _dev(cu_out).data_ptr(), ns, x.data_ptr(), table.data_ptr(), up, down,
+                                  half_len, table.shape[0], out.data_ptr(), _stream()), "jatts_resample")
+    _count(2.0 * table.shape[0] * table.shape[1] * sum(-(-o // nb) for o in n_out))
+    return out
+
+
+def wave_gain_peak(cu, n_seq, y, gain):
+    """jatts_wave_gain_peak: y_b *= gain in place (one f32 multiply) -> f32 (n_seq, 2): max |y_b| before | after the gain."""
+    lib = _abi.load()
+    y = _dev(y)
+    if y.dtype != torch.float32 or not y.is_contiguous() or cu.numel() != n_seq + 1:
+        raise ValueError("wave_gain_peak: contiguous float32 samples and n_seq + 1 offsets expected")
+    peak = torch.empty(n_seq, 2, dtype=torch.float32, device=y.device)
+    _abi.check(lib.jatts_wave_gain_peak(n_seq, _dev(cu).data_ptr(), y.data_ptr(), float(gain), peak.data_ptr(), _stream()),
+               "jatts_wave_gain_peak")
+    return peak
+
+
 # ---- stage-1 statistics (csrc/stats.hip; host layer: jatts_amd/features.py)
 def col_moments_ws_doubles(rows, dim):
     """Doubles of workspace a col_moments call over ``rows`` rows needs: two sums per column and group of rows (include/jatts_hip.h)."""

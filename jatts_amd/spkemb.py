@@ -14,12 +14,12 @@ No CPU fallback: CPU tensors or a missing libjatts_hip.so raise.
 """
 import logging
 import math
-import wave
 
 import numpy as np
 import torch
 
 from . import hip
+from .wavio import decode_wav
 from .hip import ACT_NONE, ACT_RELU, ACT_TANH
 from .models import _schema as S
 from .models._conformer import BN_EPS, PackedConv
@@ -212,23 +212,8 @@ class FbankFrontEnd:
 def load_wav(path):
     """torchaudio.load's contract for 16-bit PCM: float32 in [-1, 1) (int16 / 32768), channels averaged away never (the
     reference passes the file as is, multi-channel files become a batch there; mono is what the recipes hold)."""
-    with wave.open(path, "rb") as w:
-        sw, raw = w.getsampwidth(), w.readframes(w.getnframes())
-        if sw == 2:
-            a = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
-        elif sw == 4:
-            a = (np.frombuffer(raw, dtype="<i4").astype(np.float64) / 2147483648.0).astype(np.float32)
-        elif sw == 3:                                          # 24-bit: sign-extend the three little-endian bytes
-            b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
-            v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
-            a = ((v ^ 0x800000) - 0x800000).astype(np.float32) / 8388608.0
-        elif sw == 1:                                          # 8-bit wav is unsigned
-            a = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
-        else:
-            raise NotImplementedError(f"PCM wav with {8 * sw}-bit samples")
-        if w.getnchannels() > 1:
-            a = a.reshape(-1, w.getnchannels())[:, 0]
-        return torch.from_numpy(a.copy()), w.getframerate()
+    a, rate = decode_wav(path)                                 # (n_frames, n_channels): the decoding stage 1 shares (wavio.py)
+    return torch.from_numpy(a[:, 0].copy()), rate
 
 
 class SpkEmbExtractor:
