@@ -769,7 +769,9 @@ int jatts_lr_gather(const jatts_ragged* rg_in, const int64_t* cum, const int32_t
 
 /* Zero the rows t >= valid_len[b] of every sequence of a packed matrix x[rows][ld] (first `dim` columns; f32 or f16):
  * the `xs * x_masks` / `x * mask` steps of the reference's batched forward() passes (variance_predictor.py:81-83,
- * duration_predictor.py:93-96, matchatts/decoder.py:75-77,93-96). */
+ * duration_predictor.py:93-96, matchatts/decoder.py:75-77,93-96).  rg->len_mul scales every sequence as for jatts_hifigan_output:
+ * sequence b owns rows cu_rows[b]*len_mul .. cu_rows[b+1]*len_mul-1 and valid_len[b] counts those multiplied rows; valid_len[b] <= 0
+ * zeroes the whole sequence, valid_len[b] >= its length leaves it untouched. */
 int jatts_zero_pad_rows(const jatts_ragged* rg, void* x, int32_t dtype, int32_t ld, int32_t dim, const int32_t* valid_len,
                         void* stream);
 /* Conditional-flow-matching training pair (matchatts/flow_matching.py:115-121): per sequence b with time t[b],

@@ -602,9 +602,9 @@ __global__ __launch_bounds__(256) void lr_gather_kernel(jatts_ragged rg, const i
 template <typename T>
 __global__ __launch_bounds__(256) void zero_pad_rows_kernel(jatts_ragged rg, T* x, int ld, int dim, const int32_t* valid_len) {
   const int b = blockIdx.y;
-  const int row0 = rg.cu_rows[b];
-  const int L = rg.cu_rows[b + 1] - row0;
-  const int v = max(valid_len[b], 0);
+  const int64_t row0 = (int64_t)rg.cu_rows[b] * rg.len_mul;   // as hifigan_output_kernel: sequence b owns rows cu[b]*len_mul .. cu[b+1]*len_mul-1
+  const int L = (rg.cu_rows[b + 1] - rg.cu_rows[b]) * rg.len_mul;
+  const int v = max(valid_len[b], 0);                          // valid_len counts multiplied rows
   const int64_t n = (int64_t)(L - v) * dim;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const int64_t r = i / dim;

@@ -62,9 +62,11 @@ __global__ __launch_bounds__(256) void fbank_post_kernel(jatts_ragged rg, const 
   }
   const float floor_db = red[0] - top_db;
   for (int c = threadIdx.x; c < n_mels; c += 256) {   // n_mels <= 256
-    float s = 0.f;
-    for (int t = 0; t < T; ++t) s += fmaxf(10.f * log10f(fmaxf(p[(int64_t)(row0 + t) * ldp + c], amin)), floor_db);
-    mean[c] = s / (float)T;
+    // summed in double: a serial f32 sum of T dB values loses about sqrt(T) ulps of the running sum (4.5e-5 dB at T = 300), and the
+    // error of the mean lands on every frame of the channel
+    double s = 0.0;
+    for (int t = 0; t < T; ++t) s += (double)fmaxf(10.f * log10f(fmaxf(p[(int64_t)(row0 + t) * ldp + c], amin)), floor_db);
+    mean[c] = (float)(s / (double)T);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < T * ldo; i += 256) {
