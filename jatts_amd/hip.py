@@ -11,10 +11,11 @@ import ctypes as C
 import torch
 
 from . import _abi
+from . import precision as _precision
 from ._abi import ACT_MISH, ACT_NONE, ACT_RELU, ACT_SWISH, ACT_TANH, F16, F32, F32E, F32E6, F32S  # noqa: F401
+from .precision import EMUL, PRECISIONS  # noqa: F401  (EMUL: f32 tensors, three exact bf16 terms per operand, seven / six partial products: include/jatts_hip.h)
 
 _TORCH = {F32: torch.float32, F16: torch.float16, F32S: torch.float32, F32E: torch.float32, F32E6: torch.float32}
-EMUL = (F32E, F32E6)      # f32 tensors, three exact bf16 terms per operand: seven / six partial products per product (include/jatts_hip.h)
 
 
 def torch_dtype(code):
@@ -430,13 +431,14 @@ def pack_conv_weight_bf16x3_k32(w, c_mult=64):
     return pack_unit_weight_bf16x3_k32(wp)
 
 
-class SplitWeight:
-    """A conv weight prepared for JATTS_F32S (the pair of pack_conv_weight_split).  hip.conv1d recognises it in place of a packed f32
-    weight -- call sites stay `dtype=hip.F32` -- and takes the split kernel; shapes the split kernel does not cover (a halo beyond 32
-    rows) fall back, loudly never silently wrong, to the exact-f32 kernel on a lazily packed f32 copy of the same weight."""
+class PreparedWeight:
+    """A conv weight prepared for the kernel of dtype code ``code``: ``packed``, ``inv`` (the inverse scales of F32S, else None) and ``layout``
+    (jatts_conv_desc.w_layout).  hip.conv1d recognises it in place of a packed f32 weight -- call sites stay `dtype=hip.F32` -- and takes that
+    kernel; shapes it does not cover (conv_halo_fits) fall back, loudly never silently wrong, to the exact-f32 kernel on a lazily packed f32
+    copy of the same weight."""
+    inv, layout = None, 0
 
-    def __init__(self, w, c_mult=64):
-        self.packed, self.inv = pack_conv_weight_split(w, c_mult)
+    def __init__(self, w, c_mult):
         self._src, self._c_mult, self._f32 = w.detach(), c_mult, None
 
     def f32(self):
@@ -445,46 +447,57 @@ class SplitWeight:
         return self._f32
 
 
-class EmulWeight:
+class SplitWeight(PreparedWeight):
+    """A conv weight prepared for JATTS_F32S (the pair of pack_conv_weight_split)."""
+    code = F32S
+
+    def __init__(self, w, c_mult=64):
+        super().__init__(w, c_mult)
+        self.packed, self.inv = pack_conv_weight_split(w, c_mult)
+
+
+class EmulWeight(PreparedWeight):
     """A conv weight prepared for JATTS_F32E / JATTS_F32E6 (pack_conv_weight_bf16x3: the three bf16 terms of every weight, exact; ``code`` picks
-    seven or six partial products).  hip.conv1d recognises it in place of a packed f32 weight -- call sites stay `dtype=hip.F32` -- and takes the
-    emulated kernel; a halo beyond its staging registers (32 rows) takes the exact-f32 kernel on a lazily packed f32 copy of the same weight."""
+    seven or six partial products)."""
 
     def __init__(self, w, c_mult=64, code=F32E, layout=None):
+        super().__init__(w, c_mult)
         self.code = code
         self.layout = (1 if c_mult % 64 == 0 else 0) if layout is None else layout      # jatts_conv_desc.w_layout
         self.packed = pack_conv_weight_bf16x3_k32(w, c_mult) if self.layout else pack_conv_weight_bf16x3(w, c_mult)
-        self._src, self._c_mult, self._f32 = w.detach(), c_mult, None
-
-    def f32(self):
-        if self._f32 is None:
-            self._f32 = pack_conv_weight(self._src, F32, self._c_mult)
-        return self._f32
 
 
-_SPLIT_WEIGHTS = [0]     # 0: packed f32 weights; 1: SplitWeight (fp32_split); 2 / 3: EmulWeight, seven / six products (fp32_bf16x3 / fp32_bf16x3_6p)
-WEIGHT_MODE = {"fp16": 0, "fp32": 0, "fp32_split": 1, "fp32_bf16x3": 2, "fp32_bf16x3_6p": 3}
-EMUL_CODE = {2: F32E, 3: F32E6}
-PRECISIONS = tuple(WEIGHT_MODE)
+def conv_halo_fits(k_w, dil):
+    """The ONE fallback rule of the split and emulated conv kernels: they stage a halo of at most 32 rows; a wider conv takes the exact-f32
+    kernel on the same weight."""
+    return (k_w - 1) * dil <= 32
+
+
+_OPERAND = [F32]     # the operand code of `dtype=F32` conv call sites: F32 (packed exact f32), F32S (SplitWeight) or F32E / F32E6 (EmulWeight)
 
 
 @contextlib.contextmanager
-def split_weights(on=True):
-    """Inside: PackedConv(..., dtype=F32) packs SplitWeight operands (the models' set_precision("fp32_split")) or, with on == 2 / 3
-    ("fp32_bf16x3" / "fp32_bf16x3_6p"), EmulWeight operands.  Accepts a bool, a mode number or a precision name.  Nests."""
-    mode = WEIGHT_MODE[on] if isinstance(on, str) else int(on)
-    prev, _SPLIT_WEIGHTS[0] = _SPLIT_WEIGHTS[0], mode
+def operands(precision):
+    """Inside: PackedConv(..., dtype=F32) packs the operands of ``precision`` -- a name of PRECISIONS, a precision.Precision record, or None for
+    exact f32 (the dtype=F32 call sites of an f16-tensor precision are exact f32 too).  Nests."""
+    rec = None if precision is None else _precision.record(precision)
+    prev, _OPERAND[0] = _OPERAND[0], rec.operand if rec is not None and rec.tensors == F32 else F32
     try:
         yield
     finally:
-        _SPLIT_WEIGHTS[0] = prev
+        _OPERAND[0] = prev
+
+
+def operand_code():
+    """The operand code `dtype=F32` call sites pack for right now (hip.operands)."""
+    return _OPERAND[0]
 
 
 # Self-attention arithmetic, a switch of its own (the models' set_precision(precision, attention=...)).  None: what the precision name has always meant
 # (fp32_split: the split f16 attention; every other name: exact f32 / f16 with the tensors) -- bit for bit.  "fp32": exact f32.  "fp32_bf16x3": the
 # seven-product bf16x3 kernel (JATTS_F32E of jatts_relpos_attention) wherever emul_attention_wins says so, exact f32 elsewhere.
 ATTENTION_PRECISIONS = ("fp32", "fp32_bf16x3")
-ATTENTION_F32_PRECISIONS = ("fp32", "fp32_bf16x3", "fp32_bf16x3_6p", "fp32_split")     # the precisions whose activations are f32 tensors
+ATTENTION_F32_PRECISIONS = tuple(sorted(n for n, p in _precision.TABLE.items() if p.tensors == F32))     # the precisions whose activations are f32 tensors
 _ATTENTION = [None]
 
 
@@ -534,22 +547,31 @@ def attention_dtype(dtype, split, attention, n_heads, d_k, rel_mode):
     return F32
 
 
+def operand(code, w, c_mult=64):
+    """A conv weight prepared for operand code ``code``: SplitWeight (F32S), EmulWeight (F32E / F32E6) or the packed tensor of a plain dtype code."""
+    return SplitWeight(w, c_mult) if code == F32S else EmulWeight(w, c_mult, code) if code in EMUL else pack_conv_weight(w, code, c_mult)
+
+
 def f32_operand(w, c_mult=64):
-    """A conv weight for `dtype=F32` call sites in the current weight mode: packed exact f32, SplitWeight or EmulWeight."""
-    m = _SPLIT_WEIGHTS[0]
-    return SplitWeight(w, c_mult) if m == 1 else EmulWeight(w, c_mult, EMUL_CODE[m]) if m in EMUL_CODE else pack_conv_weight(w, F32, c_mult)
+    """A conv weight for `dtype=F32` call sites under the current hip.operands: packed exact f32, SplitWeight or EmulWeight."""
+    return operand(_OPERAND[0], w, c_mult)
 
 
-def pack_conv_weight_dev(w, dtype_code, c_mult=64, dgrad=False):
-    """pack_conv_weight as ONE HIP launch on a device f32 weight (n_out, c_in, k); dgrad=True packs the data-gradient operand
-    W'[c][n][k-1-tap] directly (no permute / flip copies).  -> (packed, padded c_in of the packed conv)."""
+def _pack_dev_args(w, c_mult, dgrad):
+    """The shared opening of the device packers: -> (library, contiguous f32 device weight, its (n, c, k), padded n_out and c_in of the packed conv)."""
     lib = _abi.load()
     w = _dev(w)
     if w.dtype != torch.float32 or not w.is_contiguous():
         w = w.float().contiguous()
     n, c, k = w.shape
     pn, pc = (c, n) if dgrad else (n, c)
-    n_pad, c_pad = round_up(pn, 32), round_up(pc, c_mult)
+    return lib, w, (n, c, k), round_up(pn, 32), round_up(pc, c_mult)
+
+
+def pack_conv_weight_dev(w, dtype_code, c_mult=64, dgrad=False):
+    """pack_conv_weight as ONE HIP launch on a device f32 weight (n_out, c_in, k); dgrad=True packs the data-gradient operand
+    W'[c][n][k-1-tap] directly (no permute / flip copies).  -> (packed, padded c_in of the packed conv)."""
+    lib, w, (n, c, k), n_pad, c_pad = _pack_dev_args(w, c_mult, dgrad)
     out = torch.empty(k * n_pad * c_pad, dtype=torch_dtype(dtype_code), device=w.device)
     _abi.check(lib.jatts_pack_conv_weight(w.data_ptr(), n, c, k, c_mult, int(dgrad), dtype_code, out.data_ptr(), _stream()),
                "jatts_pack_conv_weight")
@@ -559,13 +581,7 @@ def pack_conv_weight_dev(w, dtype_code, c_mult=64, dgrad=False):
 def pack_conv_weight_split_dev(w, c_mult=64, dgrad=False):
     """pack_conv_weight_split on the device (two launches: per-row maxima, pack), for weights that change every step (training).
     -> (packed f16, inverse scales f32 (n_pad,), padded c_in of the packed conv)."""
-    lib = _abi.load()
-    w = _dev(w)
-    if w.dtype != torch.float32 or not w.is_contiguous():
-        w = w.float().contiguous()
-    n, c, k = w.shape
-    pn, pc = (c, n) if dgrad else (n, c)
-    n_pad, c_pad = round_up(pn, 32), round_up(pc, c_mult)
+    lib, w, (n, c, k), n_pad, c_pad = _pack_dev_args(w, c_mult, dgrad)
     out = torch.empty(2 * k * n_pad * c_pad, dtype=torch.float16, device=w.device)
     inv = torch.empty(n_pad, dtype=torch.float32, device=w.device)
     _abi.check(lib.jatts_pack_conv_weight_split(w.data_ptr(), n, c, k, c_mult, int(dgrad), out.data_ptr(), inv.data_ptr(), _stream()),
@@ -577,13 +593,7 @@ def pack_conv_weight_bf16x3_dev(w, c_mult=64, dgrad=False):
     """pack_conv_weight_bf16x3_k32 (the JATTS_F32E operand, jatts_conv_desc.w_layout = 1) as ONE HIP launch on a device f32 weight (n_out, c_in, k), for
     weights that change every step (training): bit for bit the host packing.  dgrad=True packs the data-gradient operand W'[c][n][k-1-tap] directly.
     -> (packed bf16, padded c_in of the packed conv)."""
-    lib = _abi.load()
-    w = _dev(w)
-    if w.dtype != torch.float32 or not w.is_contiguous():
-        w = w.float().contiguous()
-    n, c, k = w.shape
-    pn, pc = (c, n) if dgrad else (n, c)
-    n_pad, c_pad = round_up(pn, 32), round_up(pc, c_mult)
+    lib, w, (n, c, k), n_pad, c_pad = _pack_dev_args(w, c_mult, dgrad)
     out = torch.empty(3 * k * n_pad * c_pad, dtype=torch.bfloat16, device=w.device)
     _abi.check(lib.jatts_pack_conv_weight_bf16x3(w.data_ptr(), n, c, k, c_mult, int(dgrad), out.data_ptr(), _stream()), "jatts_pack_conv_weight_bf16x3")
     return out, c_pad
@@ -617,19 +627,12 @@ def conv1d(rb, xs, w_packed, c_in, n_out, k_w, *, dtype, dil=1, pad=None, bias=N
     lib = _abi.load()
     if isinstance(xs, torch.Tensor):
         xs = [xs]
-    if isinstance(w_packed, SplitWeight):
+    if isinstance(w_packed, PreparedWeight):
         if dtype != F32:
-            raise ValueError("conv1d: a SplitWeight goes with dtype F32 tensors")
-        if (k_w - 1) * dil <= 32:
-            dtype, w_inv, w_packed, out_f32 = F32S, w_packed.inv, w_packed.packed, True
-        else:                                  # outside the split kernel's tiles: the exact-f32 kernel on the same weight
-            w_packed = w_packed.f32()
-    elif isinstance(w_packed, EmulWeight):
-        if dtype != F32:
-            raise ValueError("conv1d: an EmulWeight goes with dtype F32 tensors")
-        if (k_w - 1) * dil <= 32:
-            dtype, w_layout, w_packed, out_f32 = w_packed.code, w_packed.layout, w_packed.packed, True
-        else:
+            raise ValueError(f"conv1d: a {type(w_packed).__name__} goes with dtype F32 tensors")
+        if conv_halo_fits(k_w, dil):
+            dtype, w_inv, w_layout, w_packed, out_f32 = w_packed.code, w_packed.inv, w_packed.layout, w_packed.packed, True
+        else:                                  # outside the split / emulated kernel's tiles: the exact-f32 kernel on the same weight
             w_packed = w_packed.f32()
     x0 = _dev(xs[0])
     rows = rb.total * len_mul

@@ -55,7 +55,7 @@ class PackedConv:
             b = (b * scale if b is not None else torch.zeros_like(scale)) + shift
         self.n_out, c, self.k = w.shape
         self.c_in = hip.round_up(c, c_mult)
-        # set_precision("fp32_split"): f32 tensors, split f16 hi/lo MFMA operands (hip.split_weights is on while the model prepares)
+        # set_precision("fp32_split"): f32 tensors, split f16 hi/lo MFMA operands (hip.operands is on while the model prepares)
         # set_precision("fp32_bf16x3"): f32 tensors, three exact bf16 terms per operand, seven (fp32_bf16x3_6p: six) MFMA products (hip.EmulWeight)
         self.w = hip.f32_operand(w.to(device), c_mult) if dtype == hip.F32 else hip.pack_conv_weight(w.to(device), dtype, c_mult)
         self.b = None if b is None else b.to(device).contiguous()
@@ -97,9 +97,9 @@ class ConformerRunner:
         (FastSpeech2 / Matcha, fastspeech2.py fallback), "new" = RelPositionalEncoding +
         RelPositionMultiHeadedAttention (VITS text encoder and decoder)."""
         self.dtype, self.device, self.H = dtype, device, n_heads
-        self.split = dtype == hip.F32 and hip._SPLIT_WEIGHTS[0] == 1     # set_precision("fp32_split"): the attention takes the split arithmetic
+        self.operand = hip.operand_code() if dtype == hip.F32 else dtype   # saved: the run-time packed position operands (_pos) follow the weights'
+        self.split = self.operand == hip.F32S     # set_precision("fp32_split"): the attention takes the split arithmetic
         self.attn = hip._ATTENTION[0]     # set_precision(..., attention=): None = as the precision implies (hip.attention_dtype)
-        self.wmode = hip._SPLIT_WEIGHTS[0] if dtype == hip.F32 else 0    # the run-time packed position operands follow the weight mode
         self.rel_style = rel_style
         g = lambda k: sd[prefix + k]  # noqa: E731
         self.n_layers = 0
@@ -184,9 +184,7 @@ class ConformerRunner:
             P = hip.conv1d(rb, pe_t, L["pos"].w, L["pos"].c_in, self.A, 1, dtype=self.dtype)  # (cap, A)
             cv = hip.rowdot(P, self.A, n_pos, self.H, self.dk, L["vb"]).t().contiguous()      # (H, n_pos)
             # per-head weight operand of the BD GEMM (n = position m, contraction d_k): pure re-layout
-            pk = ((lambda w: hip.SplitWeight(w, 64)) if self.wmode == 1 else (lambda w: hip.EmulWeight(w, 64, hip.EMUL_CODE[self.wmode])) if self.wmode in hip.EMUL_CODE
-                  else (lambda w: hip.pack_conv_weight(w, self.dtype)))
-            heads = [pk(P[:, h * self.dk:(h + 1) * self.dk].float().unsqueeze(-1)) for h in range(self.H)]
+            heads = [hip.operand(self.operand, P[:, h * self.dk:(h + 1) * self.dk].float().unsqueeze(-1)) for h in range(self.H)]
             per_layer.append((heads, cv))
         if len(self._pos_cache) >= 8:
             self._pos_cache.pop(next(iter(self._pos_cache)))

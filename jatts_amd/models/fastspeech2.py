@@ -20,6 +20,7 @@ from ..graphs import GraphCache
 from ..hip import ACT_NONE, ACT_RELU, ACT_TANH
 from . import _schema as S
 from ._conformer import BN_EPS, LN_EPS, ConformerRunner, PackedConv, SpkProjection
+from ._prepared import PreparedAcoustic
 
 
 class _Predictor:
@@ -48,7 +49,7 @@ class _Predictor:
         return h
 
 
-class FastSpeech2(torch.nn.Module):
+class FastSpeech2(PreparedAcoustic, torch.nn.Module):
     def __init__(
         self,
         idim: int, odim: int, adim: int = 384, aheads: int = 4, elayers: int = 6, eunits: int = 1536,
@@ -140,50 +141,13 @@ class FastSpeech2(torch.nn.Module):
         self.stop_gradient_from_pitch_predictor = stop_gradient_from_pitch_predictor
         self.stop_gradient_from_energy_predictor = stop_gradient_from_energy_predictor
         self._train_calls = 0
-        self.precision = "fp32"   # the reference's arithmetic; set_precision("fp16") selects the fast mode
-        self.attention = None     # set_precision(..., attention=): None = the attention arithmetic the precision implies
-        self._prep = None
         self.eval()
 
-    # ------------------------------------------------------------------ weight preparation
-    def set_precision(self, precision: str, attention=None):
-        """'fp16' (f16 MFMA operands, f32 accumulate — fast mode) or 'fp32' (exact-f32 MFMA, parity mode)."""
-        # fp32_split: f32 tensors, every Conv1d / Linear but the duration predictor's on split f16 hi/lo MFMA operands (hip.SplitWeight;
-        # csrc/conv1d_split.h); fp32_bf16x3 (fp32_bf16x3_6p): the same convs on three exact bf16 terms per operand, seven (six) partial products
-        # per product (hip.EmulWeight; csrc/conv1d_emul.h)
-        # attention: the self-attention products' arithmetic, a switch of its own.  None (default) = what `precision` has always meant; "fp32_bf16x3" =
-        # the seven-product bf16x3 kernel where hip.emul_attention_wins routes it; "fp32" = exact f32.  f32 activations only (not with "fp16").
-        hip.check_attention_precision(precision, attention)
-        if precision != self.precision or attention != self.attention:
-            self.precision, self.attention, self._prep = precision, attention, None
-        return self
+    # ------------------------------------------------------------------ weight preparation (the lifecycle: _prepared.Prepared)
+    GPU_ONLY = "jatts_amd.FastSpeech2 runs on the GPU only (no CPU fallback); call .to('cuda')"
 
-    def load_state_dict(self, *a, **k):
-        self._prep = None
-        return super().load_state_dict(*a, **k)
-
-    def train(self, mode: bool = True):
-        """train(True) also turns the parameters' requires_grad on (they are created frozen for the inference path)."""
-        super().train(mode)
-        if mode:
-            self.requires_grad_(True)
-        return self
-
-    def _apply(self, fn, *a, **k):
-        self._prep = None
-        return super()._apply(fn, *a, **k)
-
-    def _prepare(self):
-        dev = self.feat_out.weight.device
-        if dev.type != "cuda":
-            raise hip._abi.JattsHipError("jatts_amd.FastSpeech2 runs on the GPU only (no CPU fallback); call .to('cuda')")
-        key = (self.precision, self.attention, str(dev))
-        if self._prep is not None and self._prep["key"] == key:
-            return self._prep
-        hip._abi.load()
-        dt = hip.F16 if self.precision == "fp16" else hip.F32
-        with hip.split_weights(self.precision), hip.attention_precision(self.attention):
-            return self._prepare_packed(dev, key, dt)
+    def _prep_device(self):
+        return self.feat_out.weight.device
 
     def _prepare_packed(self, dev, key, dt):
         sd = self.state_dict()
@@ -192,7 +156,7 @@ class FastSpeech2(torch.nn.Module):
         P["emb"] = f32(sd["encoder.embed.0.weight"])
         P["enc"] = ConformerRunner(sd, "encoder.", self.aheads, dt, dev)
         P["dec"] = ConformerRunner(sd, "decoder.", self.aheads, dt, dev)
-        with hip.split_weights(False):     # exact f32 always: durations are integers
+        with hip.operands(None):     # exact f32 always: durations are integers
             P["dur"] = _Predictor(sd, "duration_predictor.", hip.F32, dev)   # always f32: durations are integers, a
         # rounding-boundary flip under f16 would change the utterance length (the trunk is 0.3 % of the FLOPs)
         P["pitch"] = _Predictor(sd, "pitch_predictor.", dt, dev)

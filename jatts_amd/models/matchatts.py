@@ -23,6 +23,7 @@ from .. import hip
 from ..hip import ACT_MISH, ACT_NONE, ACT_RELU, ACT_SWISH
 from . import _schema as S
 from ._conformer import ConformerRunner, PackedConv, SpkProjection
+from ._prepared import PreparedAcoustic
 from .fastspeech2 import _Predictor
 
 GN_EPS = 1e-5  # torch.nn.GroupNorm / LayerNorm defaults (decoder.py:71, transformer.py:213)
@@ -88,7 +89,7 @@ class _TBlock:
     def __init__(self, sd, p, heads, dt, dev):
         f32 = lambda t: t.detach().float().to(dev).contiguous()  # noqa: E731
         self.heads = heads
-        self.split = dt == hip.F32 and hip._SPLIT_WEIGHTS[0] == 1      # set_precision("fp32_split"): the attention takes the split arithmetic too
+        self.split = dt == hip.F32 and hip.operand_code() == hip.F32S      # set_precision("fp32_split"): the attention takes the split arithmetic too
         self.attn = hip._ATTENTION[0]     # set_precision(..., attention=): None = as the precision implies (hip.attention_dtype)
         self.n1 = (f32(sd[p + "norm1.weight"]), f32(sd[p + "norm1.bias"]))
         self.n3 = (f32(sd[p + "norm3.weight"]), f32(sd[p + "norm3.bias"]))
@@ -131,7 +132,7 @@ class _TBlock:
         hip.conv1d(rb, u, self.ff2.w, self.ff2.c_in, C, 1, dtype=dt, bias=self.ff2.b, resid=x, out=x, out_f32=True)
 
 
-class _MatchaBase(torch.nn.Module):
+class _MatchaBase(PreparedAcoustic, torch.nn.Module):
     _MAS = True
 
     def __init__(
@@ -248,48 +249,13 @@ class _MatchaBase(torch.nn.Module):
         self.dropout_rates = dict(enc=transformer_enc_dropout_rate, enc_pos=transformer_enc_positional_dropout_rate,
                                   enc_attn=transformer_enc_attn_dropout_rate, dur=duration_predictor_dropout_rate, decoder=decoder_dropout)
         self._train_calls = 0
-        self.precision = "fp32"   # the reference's arithmetic; set_precision("fp16") selects the fast mode
-        self.attention = None     # set_precision(..., attention=): None = the attention arithmetic the precision implies
-        self._prep = None
         self.eval()
 
-    def train(self, mode: bool = True):
-        """train(True) also turns the parameters' requires_grad on (they are created frozen for the inference path)."""
-        super().train(mode)
-        if mode:
-            self.requires_grad_(True)
-        return self
+    # weight preparation (the lifecycle: _prepared.Prepared)
+    GPU_ONLY = "jatts_amd Matcha-TTS runs on the GPU only (no CPU fallback); call .to('cuda')"
 
-    def set_precision(self, precision, attention=None):
-        # fp32_split: f32 tensors, every Conv1d / Linear but the duration predictor's on split f16 hi/lo MFMA operands (hip.SplitWeight;
-        # csrc/conv1d_split.h); fp32_bf16x3 (fp32_bf16x3_6p): the same convs on three exact bf16 terms per operand, seven (six) partial products
-        # per product (hip.EmulWeight; csrc/conv1d_emul.h)
-        # attention: the self-attention products' arithmetic, a switch of its own.  None (default) = what `precision` has always meant; "fp32_bf16x3" =
-        # the seven-product bf16x3 kernel where hip.emul_attention_wins routes it; "fp32" = exact f32.  f32 activations only (not with "fp16").
-        hip.check_attention_precision(precision, attention)
-        if precision != self.precision or attention != self.attention:
-            self.precision, self.attention, self._prep = precision, attention, None
-        return self
-
-    def load_state_dict(self, *a, **k):
-        self._prep = None
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._prep = None
-        return super()._apply(fn, *a, **k)
-
-    def _prepare(self):
-        dev = self.encoder_proj.weight.device
-        if dev.type != "cuda":
-            raise hip._abi.JattsHipError("jatts_amd Matcha-TTS runs on the GPU only (no CPU fallback); call .to('cuda')")
-        key = (self.precision, self.attention, str(dev))
-        if self._prep is not None and self._prep["key"] == key:
-            return self._prep
-        hip._abi.load()
-        dt = hip.F16 if self.precision == "fp16" else hip.F32
-        with hip.split_weights(self.precision), hip.attention_precision(self.attention):
-            return self._prepare_packed(dev, key, dt)
+    def _prep_device(self):
+        return self.encoder_proj.weight.device
 
     def _prepare_packed(self, dev, key, dt):
         sd = self.state_dict()
@@ -297,7 +263,7 @@ class _MatchaBase(torch.nn.Module):
         P = {"key": key, "dtype": dt, "dev": dev}
         P["emb"] = f32(sd["encoder.embed.0.weight"])
         P["enc"] = ConformerRunner(sd, "encoder.", self.aheads, dt, dev)  # legacy rel-pos (matchatts_mas.py:196-218)
-        with hip.split_weights(False):     # exact f32 always: durations are integers
+        with hip.operands(None):    # exact f32 always: durations are integers
             P["dur"] = _Predictor(sd, "duration_predictor.", hip.F32, dev)   # always f32 (integer durations)
         P["eproj"] = PackedConv(sd["encoder_proj.weight"], sd["encoder_proj.bias"], dt, dev)
         if self.spk_embed_dim is not None:

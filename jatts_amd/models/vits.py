@@ -18,6 +18,7 @@ import torch
 from .. import hip
 from . import _schema as S
 from ._conformer import LN_EPS, ConformerRunner, PackedConv, SpkProjection
+from ._prepared import PreparedAcoustic
 from .fastspeech2 import _Predictor
 
 
@@ -47,7 +48,7 @@ def _wavenet_spec(spec, prefix, layers, ch, k, glob, wn=True):
         conv(q + "conv1x1_out", 2 * ch, ch, 1, True)
 
 
-class VITS(torch.nn.Module):
+class VITS(PreparedAcoustic, torch.nn.Module):
     def __init__(
         self, idim: int, odim: int, adim: int = 384, aheads: int = 4, reduction_factor: int = 1,
         text_encoder_attention_heads: int = 2, text_encoder_ffn_expand: int = 4, text_encoder_blocks: int = 6,
@@ -136,48 +137,13 @@ class VITS(torch.nn.Module):
                                   dec_pos=transformer_dec_positional_dropout_rate, dec_attn=transformer_dec_attn_dropout_rate,
                                   dur=duration_predictor_dropout_rate, post=posterior_encoder_dropout_rate, flow=flow_dropout_rate)
         self._train_calls = 0
-        self.precision = "fp32"   # the reference's arithmetic; set_precision("fp16") selects the fast mode
-        self.attention = None     # set_precision(..., attention=): None = the attention arithmetic the precision implies
-        self._prep = None
         self.eval()
 
-    def train(self, mode: bool = True):
-        """train(True) also turns the parameters' requires_grad on (they are created frozen for the inference path)."""
-        super().train(mode)
-        if mode:
-            self.requires_grad_(True)
-        return self
+    # weight preparation (the lifecycle: _prepared.Prepared)
+    GPU_ONLY = "jatts_amd.VITS runs on the GPU only (no CPU fallback); call .to('cuda')"
 
-    def set_precision(self, precision, attention=None):
-        # fp32_split: f32 tensors, every Conv1d / Linear but the duration predictor's on split f16 hi/lo MFMA operands (hip.SplitWeight;
-        # csrc/conv1d_split.h); fp32_bf16x3 (fp32_bf16x3_6p): the same convs on three exact bf16 terms per operand, seven (six) partial products
-        # per product (hip.EmulWeight; csrc/conv1d_emul.h)
-        # attention: the self-attention products' arithmetic, a switch of its own.  None (default) = what `precision` has always meant; "fp32_bf16x3" =
-        # the seven-product bf16x3 kernel where hip.emul_attention_wins routes it; "fp32" = exact f32.  f32 activations only (not with "fp16").
-        hip.check_attention_precision(precision, attention)
-        if precision != self.precision or attention != self.attention:
-            self.precision, self.attention, self._prep = precision, attention, None
-        return self
-
-    def load_state_dict(self, *a, **k):
-        self._prep = None
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._prep = None
-        return super()._apply(fn, *a, **k)
-
-    def _prepare(self):
-        dev = self.feat_out.weight.device
-        if dev.type != "cuda":
-            raise hip._abi.JattsHipError("jatts_amd.VITS runs on the GPU only (no CPU fallback); call .to('cuda')")
-        key = (self.precision, self.attention, str(dev))
-        if self._prep is not None and self._prep["key"] == key:
-            return self._prep
-        hip._abi.load()
-        dt = hip.F16 if self.precision == "fp16" else hip.F32
-        with hip.split_weights(self.precision), hip.attention_precision(self.attention):
-            return self._prepare_packed(dev, key, dt)
+    def _prep_device(self):
+        return self.feat_out.weight.device
 
     def _prepare_packed(self, dev, key, dt):
         sd = self.state_dict()
@@ -190,7 +156,7 @@ class VITS(torch.nn.Module):
         P["dec"] = ConformerRunner(sd, "decoder.", self.aheads, dt, dev, rel_style="new")
         P["te_proj"] = PackedConv(sd["text_encoder.proj.weight"], sd["text_encoder.proj.bias"], dt, dev)
         P["proj"] = SpkProjection(sd, self.adim, self.spk_embed_integration_type, dt, dev)
-        with hip.split_weights(False):     # exact f32 always: durations are integers
+        with hip.operands(None):    # exact f32 always: durations are integers
             P["dur"] = _Predictor(sd, "duration_predictor.", hip.F32, dev)   # always f32 (integer durations)
         flows = []
         for i in range(self.flow_flows):

@@ -134,6 +134,18 @@ def emul_wgrad_wins(c_in, n_out, k, rows):
     return k == 1 and rows >= 4096 and n_out * c_in >= (1 << 20)
 
 
+def _pack_conv_operand(mode, weight, dgrad):
+    """The per-step device packing of Conv1dFunction's weight in mode 0 / 1 / 2 (exact f32 / split / emulated); dgrad: the data-gradient operand
+    W'[c][n][k-1-tap].  -> (packed, padded c_in, dtype code, inverse scales or None, w_layout)."""
+    w = weight.detach()
+    if mode == 2:
+        return (*hip.pack_conv_weight_bf16x3_dev(w, dgrad=dgrad), hip.F32E, None, 1)
+    if mode == 1:
+        wp, winv, c_pad = hip.pack_conv_weight_split_dev(w, dgrad=dgrad)
+        return wp, c_pad, hip.F32S, winv, 0
+    return (*hip.pack_conv_weight_dev(w, hip.F32, dgrad=dgrad), hip.F32, None, 0)
+
+
 class Conv1dFunction(torch.autograd.Function):
     """y = conv1d(x) on a packed ragged batch (rows, c_in) -> (rows, n_out), f32; "same"-style geometry via (dil, pad).
     forward: jatts_conv1d.  backward: dx = jatts_conv1d(dy, W'[c][n][k-1-tap], pad' = (k-1) dil - pad),
@@ -143,21 +155,14 @@ class Conv1dFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, rb, dil, pad):
         n_out, c_in, k = weight.shape
-        fits = (k - 1) * dil <= 32                            # (beyond the split / emulated kernels' tiles: the exact-f32 kernel)
-        emul = EMUL_CONVS[0] and fits
-        split = SPLIT_CONVS[0] and fits and not emul
-        winv, layout, code = None, 0, hip.F32
-        if emul:
-            (wp, c_pad), layout, code = hip.pack_conv_weight_bf16x3_dev(weight.detach()), 1, hip.F32E
-        elif split:
-            (wp, winv, c_pad), code = hip.pack_conv_weight_split_dev(weight.detach()), hip.F32S
-        else:
-            wp, c_pad = hip.pack_conv_weight_dev(weight.detach(), hip.F32)
+        fits = hip.conv_halo_fits(k, dil)                     # (beyond the split / emulated kernels' tiles: the exact-f32 kernel)
+        mode = 2 if EMUL_CONVS[0] and fits else 1 if SPLIT_CONVS[0] and fits else 0
+        wp, c_pad, code, winv, layout = _pack_conv_operand(mode, weight, False)
         xin = x.contiguous() if c_in == c_pad else hip.affine_cast(x.contiguous(), hip.F32, ldy=c_pad)
         y = hip.conv1d(rb, xin, wp, c_pad, n_out, k, dtype=code, dil=dil, pad=pad,
                        bias=None if bias is None else bias.detach().contiguous(), w_inv=winv, out_f32=True, w_layout=layout)
         ctx.save_for_backward(x, weight)
-        ctx.geom = (rb, dil, pad, bias is not None, 2 if emul else 1 if split else 0, EMUL_CONVS[0])
+        ctx.geom = (rb, dil, pad, bias is not None, mode, EMUL_CONVS[0])
         return y
 
     @staticmethod
@@ -168,19 +173,14 @@ class Conv1dFunction(torch.autograd.Function):
         dy = dy.contiguous().float()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            winv, layout, code = None, 0, hip.F32
-            if mode == 2:    # the data gradient is a conv like the forward: same arithmetic
-                (wp, c_pad), layout, code = hip.pack_conv_weight_bf16x3_dev(weight.detach(), dgrad=True), 1, hip.F32E
-            elif mode == 1:  # (split: the WEIGHT gradient below stays exact f32)
-                (wp, winv, c_pad), code = hip.pack_conv_weight_split_dev(weight.detach(), dgrad=True), hip.F32S
-            else:
-                wp, c_pad = hip.pack_conv_weight_dev(weight.detach(), hip.F32, dgrad=True)       # W'[c][n][k-1-tap], packed in one launch
+            # the data gradient is a conv like the forward: same arithmetic (split: the WEIGHT gradient below stays exact f32)
+            wp, c_pad, code, winv, layout = _pack_conv_operand(mode, weight, True)       # W'[c][n][k-1-tap], packed in one launch
             dyp = dy if n_out == c_pad else hip.affine_cast(dy, hip.F32, ldy=c_pad)
             dx = hip.conv1d(rb, dyp, wp, c_pad, c_in, k, dtype=code, dil=dil, pad=(k - 1) * dil - pad, w_inv=winv, out_f32=True, w_layout=layout)
         want_db = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
             # emulated mode: the weight gradient on the same arithmetic where the shape rule says it is the faster kernel (a halo beyond 32 rows never is)
-            wcode = hip.F32E if emul_on and (k - 1) * dil <= 32 and emul_wgrad_wins(c_in, n_out, k, x.shape[0]) else hip.F32
+            wcode = hip.F32E if emul_on and hip.conv_halo_fits(k, dil) and emul_wgrad_wins(c_in, n_out, k, x.shape[0]) else hip.F32
             dw = hip.conv1d_wgrad(rb, x.detach().contiguous().float(), dy, c_in, n_out, k, dil, pad, want_db=want_db, dtype=wcode)
             if want_db:
                 dw, db = dw

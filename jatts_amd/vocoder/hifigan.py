@@ -19,31 +19,32 @@ import torch
 from .. import hip
 from ..graphs import GraphCache
 from ..models._conformer import PackedConv
+from ..models._prepared import Prepared
 from ..models import _schema as S
+from ..precision import TABLE
 
 
-class PackedSplitConv:
-    """A ResBlock conv packed for the JATTS_F32S unit: hi/lo f16 halves of w[n] * 2^s[n] + the inverse scales (hip.pack_conv_weight_split)."""
+class UnitConv:
+    """A ResBlock conv (device f32 w (C, C, k), b (C,)) packed for the fused unit of dtype code ``code`` (c_in == channels: c_mult 32).
+    F32 / F16: hip.pack_conv_weight.  F32S: hi/lo f16 halves of w[n] * 2^s[n] + the inverse scales ``inv`` (hip.pack_conv_weight_split).
+    F32E / F32E6: the three exact bf16 terms of every weight, no scales; ``k32``: in the fragment order of the 16 x 16 x 32 kernels
+    (hip.pack_unit_weight_bf16x3_k32, ``layout`` 1) instead of the 32 x 32 x 16 ones' (hip.pack_conv_weight_bf16x3, ``layout`` 0).
+    ``w_block`` is what a fused ResBlock launch takes: ``w``, but always in the 32 x 32 x 16 order (packed besides ``w`` where ``also32``)."""
 
-    def __init__(self, w, b):
+    def __init__(self, w, b, code, k32=False, also32=False):
         self.n_out, self.c_in, self.k = w.shape
-        self.w, self.inv = hip.pack_conv_weight_split(w, 32)
+        self.inv, self.layout = None, 1 if (k32 and code in hip.EMUL) else 0
+        if code == hip.F32S:
+            self.w, self.inv = hip.pack_conv_weight_split(w, 32)
+        elif code in hip.EMUL:
+            self.w = hip.pack_unit_weight_bf16x3_k32(w) if k32 else hip.pack_conv_weight_bf16x3(w, 32)
+        else:
+            self.w = hip.pack_conv_weight(w, code, 32)
+        self.w_block = hip.pack_conv_weight_bf16x3(w, 32) if (self.layout and also32) else self.w
         self.b = b.detach().float().contiguous()
 
 
-class PackedEmulConv:
-    """A ResBlock conv packed for the JATTS_F32E unit: the three exact bf16 terms of every weight, no scales; ``k32``: in the fragment order of the
-    16 x 16 x 32 kernels (hip.pack_unit_weight_bf16x3_k32, w_layout 1) instead of the 32 x 32 x 16 ones' (hip.pack_conv_weight_bf16x3, w_layout 0)."""
-
-    def __init__(self, w, b, k32=False, also32=False):
-        self.n_out, self.c_in, self.k = w.shape
-        self.layout = 1 if k32 else 0
-        self.w, self.inv = (hip.pack_unit_weight_bf16x3_k32(w) if k32 else hip.pack_conv_weight_bf16x3(w, 32)), None
-        self.w32 = hip.pack_conv_weight_bf16x3(w, 32) if (k32 and also32) else self.w      # what a fused ResBlock launch takes (always the 32 x 32 x 16 order)
-        self.b = b.detach().float().contiguous()
-
-
-class HiFiGANGenerator(torch.nn.Module):
+class HiFiGANGenerator(Prepared, torch.nn.Module):
     def __init__(self, in_channels=80, out_channels=1, channels=512, kernel_size=7,
                  upsample_scales=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4),
                  resblock_kernel_sizes=(3, 7, 11), resblock_dilations=((1, 3, 5), (1, 3, 5), (1, 3, 5)),
@@ -89,8 +90,6 @@ class HiFiGANGenerator(torch.nn.Module):
                         S._conv(spec, f"blocks.{i * nb + j}.convs2.{d}.1", c, c, rk, bias=self.bias)
         S._conv(spec, "output_conv.1", out_channels, c, kernel_size)
         S.build_from_spec(self, spec)
-        self.precision = "fp32"   # the reference's arithmetic; set_precision("fp16") selects the fast mode
-        self._prep = None
         self.eval()
 
     # checkpoints are saved with weight norm (weight_g / weight_v); fold on load
@@ -106,7 +105,6 @@ class HiFiGANGenerator(torch.nn.Module):
                 continue
             else:
                 sd[k] = v
-        self._prep = None
         return super().load_state_dict(sd, strict=strict, **kw)
 
     def remove_weight_norm(self):
@@ -122,33 +120,26 @@ class HiFiGANGenerator(torch.nn.Module):
         "fp32_bf16x3" (round 5): f32 activations everywhere, the same kernels' operands carried EXACTLY as three bf16 terms with seven MFMA
         products per product (JATTS_F32E: no scales, a one-term contraction within 2^-23 = 2 x an f32 FMA's bound; csrc/resunit_emul_impl.h,
         conv1d_emul.h); "fp32_bf16x3_6p": six products (JATTS_F32E6: dropped terms <= 2^-23 per product, 1/7 fewer pipe cycles)."""
-        if precision not in hip.PRECISIONS:
-            raise ValueError(precision)
         if precision == "fp32_split" and not self.use_additional_convs:
             raise NotImplementedError("fp32_split (JATTS_F32S) has no single-conv dilation unit: generators with use_additional_convs=False run in "
                                       "fp32, fp16, fp32_bf16x3 or fp32_bf16x3_6p")
-        if precision != self.precision:
-            self.precision, self._prep = precision, None
-        return self
+        return super().set_precision(precision)
 
-    def _apply(self, fn, *a, **k):
-        self._prep = None
-        return super()._apply(fn, *a, **k)
+    HAS_ATTENTION = False
+    GPU_ONLY = "jatts_amd HiFiGANGenerator runs on the GPU only (no CPU fallback)"
 
-    def _prepare(self):
-        dev = self.input_conv.weight.device
-        if dev.type != "cuda":
-            raise hip._abi.JattsHipError("jatts_amd HiFiGANGenerator runs on the GPU only (no CPU fallback)")
-        key = (self.precision, str(dev))
-        if self._prep is not None and self._prep["key"] == key:
-            return self._prep
-        hip._abi.load()
-        dt = hip.F16 if self.precision == "fp16" else hip.F32
-        wmode = hip.WEIGHT_MODE[self.precision]
-        split, emul = wmode == 1, wmode in hip.EMUL_CODE
+    def _prep_device(self):
+        return self.input_conv.weight.device
+
+    def _prepare_packed(self, dev, key, dt):
+        # (under hip.operands(self.precision): the input / upsampling convs take the split / emulated conv kernel too)
+        udt = TABLE[self.precision].operand        # == dt for fp16 / fp32
         sd = self.state_dict()
         f32 = lambda t: t.detach().float().to(dev).contiguous()  # noqa: E731
-        P = {"key": key, "dtype": dt, "dev": dev, "unit_dtype": hip.F32S if split else hip.EMUL_CODE[wmode] if emul else dt}
+        # the fused-ResBlock shapes of this arithmetic and the chain halo one launch covers: 64 rows (16 in exact f32)
+        fset, fhalo = {hip.F16: (self.fused_blocks, 64), hip.F32: (self.fused_blocks_f32, 16), hip.F32S: (self.fused_blocks_split, 64)}.get(
+            udt, (self.fused_blocks_emul, 64))
+        P = {"key": key, "dtype": dt, "dev": dev, "unit_dtype": udt, "fused_blocks": fset, "fused_halo": fhalo}
         nb = len(self.resblock_kernel_sizes)
         P["ups"], P["blocks"] = [], []
         supported = {hip.F16: (32, 64, 128, 256, 512), hip.F32: (32, 64, 128, 256)}[dt]
@@ -176,9 +167,7 @@ class HiFiGANGenerator(torch.nn.Module):
             return o
 
         c_prev = hip.round_up(self.channels, 64)   # input conv feeds the generic conv: 64-channel chunks
-        with hip.split_weights(wmode):      # fp32_split / fp32_bf16x3: the input / upsampling convs take the split / emulated conv kernel too
-            P["in"] = PackedConv(padw(sd["input_conv.weight"], c_prev, sd["input_conv.weight"].shape[1]),
-                                 padb(sd["input_conv.bias"], c_prev), dt, dev)
+        P["in"] = PackedConv(padw(sd["input_conv.weight"], c_prev, sd["input_conv.weight"].shape[1]), padb(sd["input_conv.bias"], c_prev), dt, dev)
         for i, (s, uk) in enumerate(zip(self.upsample_scales, self.upsample_kernel_sizes)):
             w = sd[f"upsamples.{i}.1.weight"].detach().float()            # ConvTranspose1d: (c_in, c_out, k)
             c_out = cp(w.shape[1])
@@ -187,8 +176,7 @@ class HiFiGANGenerator(torch.nn.Module):
             wp = torch.zeros(c_prev, c_out, w.shape[2], dtype=torch.float32)
             wp[: w.shape[0], : w.shape[1]] = w
             wc, pad = hip.convtranspose_as_conv(wp, s, s // 2 + s % 2)
-            with hip.split_weights(wmode):
-                pc = PackedConv(wc, padb(sd.get(f"upsamples.{i}.1.bias"), c_out).repeat(s), dt, dev)
+            pc = PackedConv(wc, padb(sd.get(f"upsamples.{i}.1.bias"), c_out).repeat(s), dt, dev)
             P["ups"].append((pc, pad, s, c_out))
             stage = []
             for j, rk in enumerate(self.resblock_kernel_sizes):
@@ -199,8 +187,7 @@ class HiFiGANGenerator(torch.nn.Module):
                     # 14 % more of that form, csrc/resunit_emul16_impl.h); the fused ResBlock launches take the 32 x 32 x 16 form (also32)
                     k32 = c_out % 32 == 0
                     also32 = self.use_additional_convs and (c_out, rk) in self.fused_blocks_emul     # (single-conv blocks are never fused)
-                    mk = (PackedSplitConv if split else (lambda w, b: PackedEmulConv(w, b, k32, also32)) if emul
-                          else (lambda w, b: PackedConv(w, b, dt, dev, c_mult=32)))   # fused unit takes c_in == channels
+                    mk = lambda w, b: UnitConv(w, b, udt, k32, also32)  # noqa: E731
                     c1 = mk(padw(sd[q + f"convs1.{di}.1.weight"], c_out, c_out).to(dev), padb(sd.get(q + f"convs1.{di}.1.bias"), c_out).to(dev))
                     # use_additional_convs=False: the single-conv unit, convs1 only
                     c2 = mk(padw(sd[q + f"convs2.{di}.1.weight"], c_out, c_out).to(dev), padb(sd.get(q + f"convs2.{di}.1.bias"), c_out).to(dev)) \
@@ -275,12 +262,10 @@ class HiFiGANGenerator(torch.nn.Module):
             for j, units in enumerate(blocks):
                 cur = up
                 # HBM-bound shapes: the whole ResBlock in one launch (x read once, y written once; residual in registers)
-                fset = (self.fused_blocks_split if udt == hip.F32S else self.fused_blocks_emul if udt in hip.EMUL
-                        else (self.fused_blocks if dt == hip.F16 else self.fused_blocks_f32))
-                if self.use_additional_convs and (c_out, units[0][2]) in fset and len(units) <= 3 \
-                        and sum((units[0][2] - 1) // 2 * (u[3] + 1) for u in units) <= (64 if (dt == hip.F16 or udt == hip.F32S or udt in hip.EMUL) else 16):
+                if self.use_additional_convs and (c_out, units[0][2]) in P["fused_blocks"] and len(units) <= 3 \
+                        and sum((units[0][2] - 1) // 2 * (u[3] + 1) for u in units) <= P["fused_halo"]:
                     lastb = fuse_mean and j == len(blocks) - 1
-                    hip.hifigan_resblock(rb, rate, cur, bufs[j][0], [(getattr(c1, "w32", c1.w), c1.b, getattr(c2, "w32", c2.w), c2.b, d) for c1, c2, _, d in units],
+                    hip.hifigan_resblock(rb, rate, cur, bufs[j][0], [(c1.w_block, c1.b, c2.w_block, c2.b, d) for c1, c2, _, d in units],
                                          c_out, units[0][2], self.slope, udt, add=outs if lastb else None,
                                          out_scale=1.0 / len(blocks) if lastb else 1.0,
                                          ws=[(c1.inv, c2.inv) for c1, c2, _, _ in units] if udt == hip.F32S else None)
@@ -294,7 +279,7 @@ class HiFiGANGenerator(torch.nn.Module):
                     # (c2 None: the single-conv unit of a generator without the additional convs)
                     hip.hifigan_resunit(rb, rate, cur, nxt, c1.w, c1.b, c2.w if c2 else None, c2.b if c2 else None, c_out, rk, d, self.slope, udt,
                                         add=outs if last else None, out_scale=1.0 / len(blocks) if last else 1.0,
-                                        ws=(c1.inv, c2.inv) if udt == hip.F32S else None, w_layout=getattr(c1, "layout", 0))
+                                        ws=(c1.inv, c2.inv) if udt == hip.F32S else None, w_layout=c1.layout)
                     cur = nxt
                 outs.append(cur)
             if fuse_mean:
