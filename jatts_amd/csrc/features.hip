@@ -5,33 +5,19 @@
 //
 // stft_mag_kernel: out[frame][bin] = | sum_n x[refl(frame * hop + n - n_fft / 2)] * (w[n] cos(2 pi n bin / N) - i w[n] sin(2 pi n bin / N)) |
 //   * the window is folded into the table on the host (float64, rounded once): table[n][col], col < nbp the cosines, nbp + col the sines;
-//   * A operand = frames.  A workgroup stages 64 frames x 64 samples of the current K-chunk into an LDS tile [64][64 + 4] (row bytes + 16:
-//     the two ds_read_b128 of a fragment are conflict-free, see below), applying numpy's reflect rule while it stages; the overlapping rows
-//     are re-read from L2 (n_fft / hop reads per sample).  Reading span[f * hop + n] from one staged span instead would put the 32 frame
-//     lanes hop floats apart: at hop 256 all on one bank.  Neither the frame matrix nor the complex spectrum ever reaches HBM;
-//   * B operand = the table, straight from L2 into registers (one step ahead): lane l of k-step s reads table[16 s + 8 (l >> 5) + j][col0 + (l & 31)],
-//     128 contiguous bytes per half wave.  The table is the traffic (16.8 MB at n_fft 2048 against 1.2 KB of samples per frame): a workgroup
-//     owns 128 bins (4 waves x 32 bins, cosine and sine tile of the same bins in the same lane) and the grid runs frame tiles fastest, bin
-//     tiles slowest, so the workgroups resident at any time walk the same 2 MB slice of the table together;
-//   * v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain, the arithmetic of every exact kernel here.  Lane half h consumes
-//     k = 16 s + 8 h + j in MFMA j -- the same samples meet the same table rows in both operands, the order of the sum is fixed.
-//     The sum has TWO levels: every 64-sample chunk is a chain of its own, started at zero, and the chunks are added in order (v_add_f32,
-//     64 per 128 MFMAs).  One 2048-term chain rounds 2048 times at the magnitude of the growing sum (error ~ sqrt(K)); with chunks it is 64
-//     roundings at a chunk's magnitude plus 32 at the sum's.  A CPU emulation of both orders on the test signals: one chain 6.0-7.6 x the
-//     float32-FFT error on mel bins relative to their frame's maximum, chunks of 64 1.2-1.5 x (profiles/r15_notes.md);
+//   * the contraction itself is framed_contract<2> (framed_contraction.h: tile staging, the banking argument, the wave dealing and why the
+//     sum runs in 64-term chunks added in order): A operand = frames of n_fft samples hop apart, read under numpy's reflect rule while they are
+//     staged.  Reading span[f * hop + n] from one staged span instead would put the 32 frame lanes hop floats apart: at hop 256 all on one bank.
+//     Neither the frame matrix nor the complex spectrum ever reaches HBM;
+//   * B operand = the table, both planes of a bin in the same lane (cosine and sine tile of the same 32 bins per wave), so |.| is the epilogue.
+//     The table is the traffic (16.8 MB at n_fft 2048 against 1.2 KB of samples per frame, n_fft / hop reads per sample): the grid runs frame
+//     tiles fastest, bin tiles slowest, so the workgroups resident at any time walk the same 2 MB slice of the table together;
 //   * pow_sum: per (workgroup, frame) the sum of re^2 + im^2 over the workgroup's bins in a fixed tree (lanes, then waves), stored to the
 //     reduction scratch; a second launch adds the bin tiles in order.  No atomics: a frame's bits depend on its own samples only.
 #include "det_reduce.h"
+#include "framed_contraction.h"
 
 namespace {
-
-constexpr int FT = 64;         // frames per workgroup (two 32-row MFMA tiles)
-constexpr int KC = 64;         // samples per staged K-chunk
-constexpr int PITCH = KC + 4;  // floats; row bytes + 16
-constexpr int BW = 128;        // bins per workgroup (4 waves x 32)
-
-// LDS banks of the A fragment reads (ds_read_b128, banks (a / 4) mod 64, lane groups {0-3, 12-15, 20-27} ...): lane (f, h) reads 4 floats at
-// f * 68 + 16 s + 8 h (+ 4): bank 4 f mod 64 + const for the 16 different f of a group -- 16 distinct 4-bank slots, conflict-free.
 
 __device__ __forceinline__ int reflect_index(int p, int L) {
   p = p < 0 ? -p : p;
@@ -49,94 +35,16 @@ __global__ __launch_bounds__(256, 2) void stft_mag_kernel(jatts_ragged rg, const
   if (t0 >= T) return;
   const int s0 = cu_samples[b], L = cu_samples[b + 1] - s0;
   const float* xb = x + s0;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int h = lane >> 5, c = lane & 31;
-  // Work of a wave: one 32-bin tile x both frame tiles.  The last workgroup of a row of bin tiles may own fewer than four bin tiles (n_bins =
-  // n_fft / 2 + 1: ONE at every power of two); with one or two, its (bin tile, frame tile) pairs are dealt one per wave, which halves its time.
-  // A frame tile wholly past the utterance's end is skipped.  fmask: the frame tiles this wave computes (wave-uniform, held in an SGPR).
-  const int ntl = min(4, (nbp >> 5) - (int)blockIdx.z * 4);
-  const bool pairs = ntl <= 2;
-  const int slot = pairs ? wave >> 1 : wave;
-  const unsigned fmask = __builtin_amdgcn_readfirstlane(slot >= ntl ? 0u : (pairs ? 1u << (wave & 1) : 3u) & (t0 + 32 < T ? 3u : 1u));
-  const int bin0 = blockIdx.z * BW + slot * 32;
-  const bool live = fmask != 0;               // a wave without work only helps staging
-  const int ldt = 2 * nbp;
+  const framed_wave w = framed_deal(nbp, t0, T);      // one 32-bin tile (n_bins = n_fft / 2 + 1: ONE in the last workgroup at every power of two)
+  const int slot = w.slot, bin0 = w.col0;
+  const unsigned fmask = w.fmask;
   const int half = n_fft >> 1;
 
-  // staging map: thread -> sample column tid & 63 of frames (tid >> 6) + 4 i (a wave writes one 256-byte row: conflict-free)
-  const int sn = tid & 63, sf = tid >> 6;
-  float xr[16];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int t = t0 + sf + 4 * i;
-      xr[i] = t < T ? xb[reflect_index(t * hop + k0 + sn - half, L)] : 0.f;
-    }
-  };
-  auto stash = [&](float* buf) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) buf[(sf + 4 * i) * PITCH + sn] = xr[i];
-  };
-
-  const float* tb = table + (live ? bin0 + c : 0);
-  auto load_b = [&](int s, f32x8& re, f32x8& im) {
-    const float* q = tb + (int64_t)(16 * s + 8 * h) * ldt;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      re[j] = q[(int64_t)j * ldt];
-      im[j] = q[(int64_t)j * ldt + nbp];
-    }
-  };
-
   f32x16 acc[2][2];     // [frame tile][re | im]
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[f][q][r] = 0.f;
-
-  const int n_chunks = n_fft / KC, n_steps = n_fft / 16;
-  f32x8 bre, bim, nre, nim;
-  if (live) load_b(0, nre, nim);
-  fetch(0);
-  stash(tile[0]);
-  __syncthreads();
-  for (int ch = 0; ch < n_chunks; ++ch) {
-    const float* cur = tile[ch & 1];
-    if (ch + 1 < n_chunks) fetch((ch + 1) * KC);
-    if (live) {
-      f32x16 part[2][2];      // this chunk's 64-term chains, started at zero
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) part[f][q][r] = 0.f;
-#pragma unroll
-      for (int ss = 0; ss < KC / 16; ++ss) {
-        const int s = ch * (KC / 16) + ss;
-        bre = nre;
-        bim = nim;
-        load_b(s + 1 < n_steps ? s + 1 : s, nre, nim);      // one step ahead; the last step is read twice
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-          if (!(fmask >> f & 1)) continue;
-          const float* p = cur + (f * 32 + c) * PITCH + 16 * ss + 8 * h;
-          const f32x4 lo = *reinterpret_cast<const f32x4*>(p), hi = *reinterpret_cast<const f32x4*>(p + 4);
-          const f32x8 a = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          mma32(a, bre, part[f][0]);
-          mma32(a, bim, part[f][1]);
-        }
-      }
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) acc[f][q] += part[f][q];      // chunks in order: the second level of the sum
-    }
-    if (ch + 1 < n_chunks) stash(tile[(ch + 1) & 1]);       // last read two barriers ago
-    __syncthreads();
-  }
+  framed_contract<2>(tile, t0, T, n_fft, table + (fmask ? bin0 + c : 0), 2 * nbp, nbp, fmask,
+                     [&](int t, int k) { return xb[reflect_index(t * hop + k - half, L)]; }, acc);
 
   // epilogue: C fragment col = lane & 31 (bin), row = (r & 3) + 8 (r >> 2) + 4 h (frame): 128-byte row segments per half wave
   const int bin = bin0 + c;

@@ -3,28 +3,19 @@
 // parity with librosa / soxr_hq is UNPINNED.
 //
 // resample_kernel: y[m] = sum_n h[m * down - n * up + half_len] * x[n], zeros beyond both ends of the utterance, as ONE exact-f32 framed
-// contraction -- stft_mag_kernel (features.hip) with zero padding instead of reflection, a plain store as the epilogue, and the frame = a
-// BLOCK of Nb = up * r consecutive outputs (every block meets the taps in the same phase pattern, so one table serves them all):
+// contraction (framed_contract<1>, framed_contraction.h: the loop, its LDS tile, the wave dealing and the order of the sum live there).  The
+// frame = a BLOCK of Nb = up * r consecutive outputs (every block meets the taps in the same phase pattern, so one table serves them all):
 //   Y[q][c] = sum_i X_q[i] * W[i][c],  X_q[i] = x[q * hop_b - L + i],  W[i][c] = h[c * down - (i - L) * up + half_len] or 0,
 //   hop_b = down * r, L = half_len / up, i < K.  Row q of Y is outputs q * Nb .. q * Nb + Nb - 1: the rows concatenated are the waveform.
-//   * A operand = blocks.  A workgroup stages 64 blocks x 64 samples of the current K-chunk into an LDS tile [64][64 + 4] (row bytes + 16:
-//     the two ds_read_b128 of a fragment are conflict-free, as in features.hip), writing zeros for samples outside the utterance; the
-//     overlapping rows are re-read from L2;
-//   * B operand = the table [K][Nbp] (jatts_amd.features.resample_table), straight from L2 into registers one k-step ahead: lane l of step s
-//     reads W[16 s + 8 (l >> 5) + j][col0 + (l & 31)].  A workgroup owns 128 columns (4 waves x 32) and the grid runs block tiles fastest;
-//   * v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain.  Two levels as in the STFT: every 64-sample chunk is a chain of its own,
-//     started at zero, and the chunks are added in order.  No atomics: an utterance's bits depend on its own samples and the table only,
-//     not on its place in the batch;
+//   * A operand = blocks, zeros for samples outside the utterance;
+//   * B operand = the table [K][Nbp] (jatts_amd.features.resample_table), one plane; the grid runs block tiles fastest.  With one or two column
+//     tiles (up <= 64: every 2:1, 3:1, 3:2 conversion) the (column tile, block tile) pairs are dealt one per wave;
+//   * no atomics: an utterance's bits depend on its own samples and the table only, not on its place in the batch;
 //   * outputs at or beyond n_out are never stored.
 // wave_gain_peak_kernel: the two checks of read_audio (utils.py:221-232) and its gain without a read-back per utterance.
-#include "common.h"
+#include "framed_contraction.h"
 
 namespace {
-
-constexpr int FT = 64;         // blocks per workgroup (two 32-row MFMA tiles)
-constexpr int KC = 64;         // samples per staged K-chunk
-constexpr int PITCH = KC + 4;  // floats; row bytes + 16
-constexpr int BW = 128;        // table columns per workgroup (4 waves x 32)
 
 struct resample_geom {
   int r, nb, nbp, hop_b, L, K;
@@ -52,81 +43,19 @@ __global__ __launch_bounds__(256, 2) void resample_kernel(const int32_t* __restr
   if (t0 >= T) return;
   const int s0 = cu_in[b], n_in = cu_in[b + 1] - s0;
   const float* xb = x + s0;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lane = threadIdx.x & 63;
   const int h = lane >> 5, c = lane & 31;
-  // Work of a wave: one 32-column tile x both block tiles; with one or two column tiles (up <= 64: every 2:1, 3:1, 3:2 conversion) the
-  // (column tile, block tile) pairs are dealt one per wave.  fmask: the block tiles this wave computes (wave-uniform).
-  const int ntl = min(4, (nbp >> 5) - (int)blockIdx.z * 4);
-  const bool pairs = ntl <= 2;
-  const int slot = pairs ? wave >> 1 : wave;
-  const unsigned fmask = __builtin_amdgcn_readfirstlane(slot >= ntl ? 0u : (pairs ? 1u << (wave & 1) : 3u) & (t0 + 32 < T ? 3u : 1u));
-  const int col0 = blockIdx.z * BW + slot * 32;
-  const bool live = fmask != 0;               // a wave without work only helps staging
+  const framed_wave w = framed_deal(nbp, t0, T);
+  const int col0 = w.col0;
+  const unsigned fmask = w.fmask;
 
-  // staging map: thread -> sample column tid & 63 of blocks (tid >> 6) + 4 i (a wave writes one 256-byte row: conflict-free)
-  const int sn = tid & 63, sf = tid >> 6;
-  float xr[16];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int t = t0 + sf + 4 * i;
-      const int p = t * hop_b - L + k0 + sn;
-      xr[i] = (t < T && p >= 0 && p < n_in) ? xb[p] : 0.f;      // zeros lie beyond both ends
-    }
-  };
-  auto stash = [&](float* buf) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) buf[(sf + 4 * i) * PITCH + sn] = xr[i];
-  };
-
-  const float* tb = table + (live ? col0 + c : 0);
-  auto load_b = [&](int s, f32x8& w) {
-    const float* q = tb + (int64_t)(16 * s + 8 * h) * nbp;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) w[j] = q[(int64_t)j * nbp];
-  };
-
-  f32x16 acc[2];     // [block tile]
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[f][r] = 0.f;
-
-  const int n_chunks = K / KC, n_steps = K / 16;
-  f32x8 bw, nw;
-  if (live) load_b(0, nw);
-  fetch(0);
-  stash(tile[0]);
-  __syncthreads();
-  for (int ch = 0; ch < n_chunks; ++ch) {
-    const float* cur = tile[ch & 1];
-    if (ch + 1 < n_chunks) fetch((ch + 1) * KC);
-    if (live) {
-      f32x16 part[2];      // this chunk's 64-term chains, started at zero
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) part[f][r] = 0.f;
-#pragma unroll
-      for (int ss = 0; ss < KC / 16; ++ss) {
-        const int s = ch * (KC / 16) + ss;
-        bw = nw;
-        load_b(s + 1 < n_steps ? s + 1 : s, nw);      // one step ahead; the last step is read twice
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-          if (!(fmask >> f & 1)) continue;
-          const float* p = cur + (f * 32 + c) * PITCH + 16 * ss + 8 * h;
-          const f32x4 lo = *reinterpret_cast<const f32x4*>(p), hi = *reinterpret_cast<const f32x4*>(p + 4);
-          const f32x8 a = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          mma32(a, bw, part[f]);
-        }
-      }
-#pragma unroll
-      for (int f = 0; f < 2; ++f) acc[f] += part[f];      // chunks in order: the second level of the sum
-    }
-    if (ch + 1 < n_chunks) stash(tile[(ch + 1) & 1]);       // last read two barriers ago
-    __syncthreads();
-  }
+  f32x16 acc[2][1];     // [block tile][the one plane]
+  framed_contract<1>(tile, t0, T, K, table + (fmask ? col0 + c : 0), nbp, 0, fmask,
+                     [&](int t, int k) {
+                       const int p = t * hop_b - L + k;
+                       return (p >= 0 && p < n_in) ? xb[p] : 0.f;      // zeros lie beyond both ends
+                     },
+                     acc);
 
   // epilogue: C fragment col = lane & 31 (table column), row = (r & 3) + 8 (r >> 2) + 4 h (block): 128-byte segments per half wave, and
   // consecutive blocks are consecutive in the waveform
@@ -140,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void resample_kernel(const int32_t* __restr
     for (int r = 0; r < 16; ++r) {
       const int fl = f * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
       const int m = (t0 + fl) * nb + col;
-      if (m < n_out) yb[m] = acc[f][r];
+      if (m < n_out) yb[m] = acc[f][0][r];
     }
   }
 }
