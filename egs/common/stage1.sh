@@ -5,7 +5,9 @@
 # ${dumpdir}/${train_set}/stats.npz.  Differences: ONE GPU process per set does the whole csv in ragged batches (no csv split, no
 # train_cmd, no background jobs), the test set is extracted too, and the dumps and the statistics are .npz (the format the later
 # stages here read; tools/h5stats_to_npz.py goes the other way for a reference-made stats.h5).  A config that lists pitch (the
-# FastSpeech2 ones) is refused by the CLI with its message: nothing is skipped silently.  Runs under the caller's set -euo pipefail:
+# FastSpeech2 ones) with pitch_extract_type: dio is refused by the CLI with its message: nothing is skipped silently.  With
+# pitch_extract_type: acf the CLI extracts pitch with this package's own autocorrelation estimator (parity with DIO UNPINNED), reading
+# the speakers' ranges from conf/f0.yaml where it exists.  Runs under the caller's set -euo pipefail:
 # the first failing step ends the stage.
 # shellcheck disable=SC2154
 stage1_features() {

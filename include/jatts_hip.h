@@ -723,6 +723,41 @@ int jatts_resample(int32_t n_seq, const int32_t* cu_in, const int32_t* cu_out, c
 int jatts_wave_gain_peak(int32_t n_seq, const int32_t* cu, float* y, float gain, float* peak, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Stage-1 pitch (additive to ABI 7): the F0 track jatts/modules/feature_extract/dio.py:100-109 takes from pyworld
+ * (DIO + StoneMask), here an autocorrelation estimator of this project's own definition (Boersma 1993 on the STFT's frames; the
+ * definition is written out in jatts_amd/csrc/pitch.hip and DESIGN 7 f.8), pinned on a float64 restatement.  Parity with DIO /
+ * StoneMask is UNPINNED.  The steps after the raw track (dio.py:110-159) are pinned on the real Dio.forward; _adjust_num_frames
+ * and _average_by_duration are jatts_energy_adjust and jatts_token_average unchanged.
+ * ------------------------------------------------------------------------------- */
+/* Autocorrelation of every frame from its magnitude spectrum (replaces the analysis inside pyworld.dio, dio.py:102-108):
+ *   r[row][tau] = sum_{k<K} mag[row][k]^2 * table[k][tau],  tau < Lp,
+ * an exact-f32 MFMA contraction with the fixed two-level order of jatts_stft_mag and jatts_resample (a chain per 64 rows of the
+ * table, chains added in order; no atomics): a frame's bits depend on its own row and the table only.  mag: [rows][ldm] f32 as
+ * jatts_stft_mag writes it with ldo = ldm >= K (its padding columns zero), K = n_bins rounded up to 64.  table: [K][Lp] f32, Lp =
+ * hi + 2 rounded up to 32: c_k cos(2 pi k tau / n_fft) / n_fft * rw(0) / rw(tau) folded in float64 and rounded once, padding rows and
+ * columns zero (jatts_amd.features.acf_table).  r: [rows][Lp]; nothing is written past the last row.
+ * JATTS_ERR_ARG: K not a multiple of 64 in [64, 1088], Lp not a multiple of 32 in [32, 2048], ldm < K. */
+int jatts_acf_from_mag(const jatts_ragged* rg_frames, const float* mag, int32_t ldm, const float* table, int32_t K, int32_t Lp,
+                       float* r, void* stream);
+/* Candidate picking and voicing per frame (replaces pyworld.dio's candidate selection and pyworld.stonemask's refinement,
+ * dio.py:102-109): with rho(tau) = r[row][tau] / max(r[row][0], 1e-30), every tau in [lo, hi] with rho(tau) >= rho(tau-1) and
+ * rho(tau) > rho(tau+1) is a candidate; a, b, c = rho(tau-1), rho(tau), rho(tau+1), den = a - 2b + c, off = clip(0.5 (a - c) / den,
+ * -0.5, 0.5) if den < 0 else 0, peak = b - 0.25 (a - c) off, score = peak - octave_cost * log2((tau + off) * f0min / sr); the
+ * highest score wins, equal scores go to the smallest tau.  Voiced iff a candidate exists, peak >= voicing_threshold and
+ * sqrt(r[row][0] / sum_w2) >= silence_threshold * peak[b * peak_stride] (max |x| of utterance b: what jatts_wave_gain_peak writes,
+ * stride 2).  f0[row] = sr / (tau + off) when voiced, else 0; tau (optional, int32 [rows]): the winner's lag, 0 without a candidate.
+ * One wave per frame, no atomics.  JATTS_ERR_ARG: lo < 2, hi < lo, ldr < hi + 2, a non-positive peak_stride, sr, f0min or sum_w2. */
+int jatts_pitch_pick(const jatts_ragged* rg_frames, const float* r, int32_t ldr, const float* peak, int32_t peak_stride, int32_t lo,
+                     int32_t hi, float sr, float f0min, float sum_w2, float voicing_threshold, float silence_threshold,
+                     float octave_cost, float* f0, int32_t* tau, void* stream);
+/* _convert_to_continuous_f0 (dio.py:125-146; use_continuous != 0) and the log of the non-zero values (dio.py:112-114; use_log != 0)
+ * per utterance: frames before the first voiced one take its value, frames after the last voiced one take that one's, unvoiced
+ * frames between two voiced ones p < t < n become f0[p] + (t - p) * ((f0[n] - f0[p]) / (n - p)) in f32 (one fused multiply-add), an
+ * all-unvoiced track stays zeros; the logarithm is correctly rounded.  out must not alias f0 (JATTS_ERR_ARG). */
+int jatts_f0_continuous_log(const jatts_ragged* rg_frames, const float* f0, int32_t use_continuous, int32_t use_log, float* out,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Stage-1 statistics and normalisation (additive to ABI 7): the per-feature sklearn StandardScaler of
  * jatts/bin/compute_statistics.py:75-103 (partial_fit per utterance, float64) as a running state on the device, and the
  * StandardScaler.transform of jatts/datasets/tts_dataset.py:69-145.

@@ -4,13 +4,17 @@ on the GPU.
 Same flags (``--csv --dumpdir --config [--f0_path] [--verbose]``, preprocess.py:39-66) plus ``--batch-size`` (utterances per ragged
 launch, default 32) and ``--dump-format`` (``npz``, the default and the pinned path, or ``h5`` where h5py is importable: unpinned).
 The config keys are the recipes': ``sampling_rate``, ``fft_size``, ``hop_size``, ``win_length``, ``window``, ``num_mels``, ``fmin``,
-``fmax``, ``global_gain_scale``, ``feat_list``, ``log_base``.
+``fmax``, ``global_gain_scale``, ``feat_list``, ``log_base``; for pitch ``pitch_extract_type``, ``pitch_extract_f0min``,
+``pitch_extract_f0max`` and, optionally, ``pitch_voicing_threshold``, ``pitch_silence_threshold``, ``pitch_octave_cost``.
 
 Per batch the utterances are grouped by their files' native rate and every group is read -> ``jatts_resample`` ->
 ``jatts_wave_gain_peak`` -> ``LogMelExtractor`` in batched, ragged launches (``features.read_audio_batch``).  ``energy`` runs through
 ``features.Energy`` (the csv must carry ``durations``), ``spkemb`` through ``spkemb.SpkEmbExtractor`` with its "unverified" warning.
-``pitch`` (DIO needs pyworld) and the ``encodec*`` types (the encodec package) are refused with a NotImplementedError before any file
-is written; a ``--f0_path`` without ``pitch`` in the list is accepted and ignored.
+``pitch`` runs through ``features.Pitch`` when ``pitch_extract_type`` is ``acf``: this package's own autocorrelation estimator, whose parity
+with the reference's DIO + StoneMask is UNPINNED (a warning says so); the steps after the raw track are the reference's.  The f0 range
+comes from ``--f0_path`` by speaker (``item["spk"]``) or from the config (preprocess.py:263-270), a batch's utterances are grouped by their
+range, and the csv must carry ``durations``.  ``pitch_extract_type: dio`` (pyworld) and the ``encodec*`` types (the encodec package) are
+refused with a NotImplementedError before any file is written; a ``--f0_path`` without ``pitch`` in the list is accepted and ignored.
 
 Every kept utterance becomes ``<dumpdir>/<sample_id>.npz`` (entries ``wave``, ``mel``, ... in float32: what
 ``jatts_amd.bin.compute_statistics`` reads), written once, and the csv is rewritten with a ``feat_path`` column
@@ -35,19 +39,31 @@ from jatts_amd import features
 _LOG_FORMAT = "%(asctime)s (%(module)s:%(lineno)d) %(levelname)s: %(message)s"
 _MISSING = {
     "pitch": "feat_list holds 'pitch': the reference extracts it with DIO through pyworld, which is not installed here and has no "
-             "kernel in this package; remove 'pitch' from feat_list or run the reference's preprocess.py for this config",
+             "kernel in this package; remove 'pitch' from feat_list or run the reference's preprocess.py for this config. "
+             "pitch_extract_type: acf selects this package's own autocorrelation estimator (parity with DIO unpinned).",
     "encodec": "feat_list holds '{}': EnCodec tokens need the encodec package, which is not installed here and has no kernel in this package",
 }
 _ENCODEC = ("encodec", "encodec_24khz", "encodec_48khz")
+_ACF_WARNING = ("pitch_extract_type acf: F0 comes from this package's own autocorrelation estimator; parity with the reference's DIO + "
+                "StoneMask is UNPINNED (the steps after the raw track are pinned on the reference)")
 
 
 def check_feat_list(config):
-    """The feature types this CLI serves, in the config's order.  Raises before anything is written: NotImplementedError for pitch and
-    encodec*, ValueError for the extractor types the reference refuses too (preprocess.py:122-150)."""
+    """The feature types this CLI serves, in the config's order.  Raises before anything is written: NotImplementedError for DIO pitch and
+    encodec*, ValueError for the extractor types the reference refuses too (preprocess.py:122-150).  pitch_extract_type acf is accepted
+    with a warning that its parity with DIO is unpinned."""
     feats = list(config.get("feat_list", ["mel"]))
+    warned = False
     for f in feats + list(config.get("prompt_feat_list", [])):
         if f == "pitch":
-            raise NotImplementedError(_MISSING["pitch"])
+            kind = config.get("pitch_extract_type")
+            if kind in (None, "dio"):
+                raise NotImplementedError(_MISSING["pitch"])
+            if kind != "acf":
+                raise ValueError(f"Unsupported pitch extractor type: {kind}")       # preprocess.py:123-125
+            if not warned:
+                logging.warning(_ACF_WARNING)
+                warned = True
         if f in _ENCODEC:
             raise NotImplementedError(_MISSING["encodec"].format(f))
     if "energy" in feats and config.get("energy_extract_type") != "energy":
@@ -93,7 +109,7 @@ def main(argv=None):
     p.add_argument("--csv", required=True, type=str, help="csv file.")
     p.add_argument("--dumpdir", type=str, required=True, help="directory to dump feature files.")
     p.add_argument("--config", type=str, required=True, help="yaml format configuration file.")
-    p.add_argument("--f0_path", default=None, type=str, help="file storing f0 ranges (read only by pitch extraction, which is refused)")
+    p.add_argument("--f0_path", default=None, type=str, help="file storing f0 ranges (read only when feat_list holds pitch)")
     p.add_argument("--verbose", type=int, default=1, help="logging level. higher is more logging. (default=1)")
     p.add_argument("--batch-size", type=int, default=32, help="utterances per ragged launch (default=32)")
     p.add_argument("--dump-format", choices=("npz", "h5"), default="npz", help="npz (default, pinned) or h5 (needs h5py; unpinned)")
@@ -115,12 +131,22 @@ def main(argv=None):
 
     # everything that can refuse does so here, before the first file is written
     feats = check_feat_list(config)
-    known = [f for f in feats if f in ("mel", "energy", "spkemb")]
+    known = [f for f in feats if f in ("mel", "pitch", "energy", "spkemb")]
     for f in feats:
         if f not in known:
             logging.info(f"Not supported feature type {f}. Skip.")
     if "energy" in known and any(_none_if_empty(item.get("durations")) is None for item in dataset):
         raise ValueError("feat_list holds 'energy': every row of the csv needs a durations column (token-averaged energy)")
+    f0_all = None
+    if "pitch" in known:
+        if any(_none_if_empty(item.get("durations")) is None for item in dataset):
+            raise ValueError("feat_list holds 'pitch': every row of the csv needs a durations column (token-averaged f0)")
+        if args.f0_path is not None:                                         # preprocess.py:94-99
+            with open(args.f0_path) as f:
+                f0_all = yaml.load(f, Loader=yaml.Loader)
+            for item in dataset:
+                if item.get("spk") not in f0_all:
+                    raise KeyError(f"{args.f0_path} has no f0 range for speaker {item.get('spk')!r} ({item.get('sample_id')})")
     write = _h5_writer() if args.dump_format == "h5" else _npz_writer()
     if not dataset:
         raise ValueError(f"{args.csv} lists no utterance")
@@ -135,6 +161,20 @@ def main(argv=None):
         energy_ex = features.Energy(fs=sr, n_fft=config["fft_size"], win_length=config["win_length"], hop_length=config["hop_size"],
                                     window=config["window"], use_token_averaged_energy=True,
                                     reduction_factor=config["model_params"]["reduction_factor"], device=device)
+    pitch_ex = None
+    if "pitch" in known:
+        pitch_ex = features.Pitch(fs=sr, n_fft=config["fft_size"], hop_length=config["hop_size"], use_token_averaged_f0=True,
+                                  use_continuous_f0=True, use_log_f0=True, reduction_factor=config["model_params"]["reduction_factor"],
+                                  voicing_threshold=config.get("pitch_voicing_threshold", features.PITCH_VOICING_THRESHOLD),
+                                  silence_threshold=config.get("pitch_silence_threshold", features.PITCH_SILENCE_THRESHOLD),
+                                  octave_cost=config.get("pitch_octave_cost", features.PITCH_OCTAVE_COST), device=device)
+
+        def f0_range(item):                                                  # preprocess.py:263-270
+            if f0_all is not None:
+                return f0_all[item["spk"]]["f0min"], f0_all[item["spk"]]["f0max"]
+            return config["pitch_extract_f0min"], config["pitch_extract_f0max"]
+        for rng in sorted({f0_range(item) for item in dataset}):             # a range the geometry refuses ends the run here
+            features.pitch_geometry(sr, config["fft_size"], *rng)
     spk_ex = None
     if "spkemb" in known:
         from jatts_amd.spkemb import SpkEmbExtractor
@@ -171,6 +211,17 @@ def main(argv=None):
                     assert total == feat.shape[0], \
                         f"{item['sample_id']}: mel duration {feat.shape[0]} and phoneme durations {total} don't match ."
                 entries[i]["mel"] = np.ascontiguousarray(feat, dtype=np.float32)
+        if pitch_ex is not None:
+            by_range = {}
+            for i, (item, _) in enumerate(kept):
+                by_range.setdefault(f0_range(item), []).append(i)
+            for (f0min, f0max), members in by_range.items():                 # one ragged run per range, as read_audio_batch groups by rate
+                sub = pw if len(members) == len(kept) else features.PackedWaves(
+                    torch.cat([kept[i][1] for i in members]).contiguous(), [int(kept[i][1].numel()) for i in members])
+                # (feat_length = len(mel), preprocess.py:272-276: the track has the mel's frames already)
+                pit = pitch_ex.extract(sub, f0min, f0max, None, [durations[i] for i in members])
+                for i, v in zip(members, pit):
+                    entries[i]["pitch"] = v.cpu().numpy().astype(np.float32)
         if energy_ex is not None:
             en = energy_ex._ex.energy(pw, [sum(d) for d in durations], durations)
             for i, e in enumerate(en):

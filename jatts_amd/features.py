@@ -10,7 +10,12 @@ GPU only: a CPU device or a missing library raises ``JattsHipError``.  torch / n
 
 librosa itself is absent from the build environment, so parity with it is NOT pinned; the tests pin this module on
 ``torch.stft`` in float64 and on ``transformers.audio_utils.mel_filter_bank(norm="slaney", mel_scale="slaney")``.
-Pitch (WORLD / DIO) stays out of scope.
+
+Pitch is here too (``Pitch``, the reference's ``feature_extract/dio.py:21-159``): the reference extracts F0 with DIO + StoneMask through
+pyworld, which is absent from the build environment, so the raw track comes from an autocorrelation estimator of our own definition
+(Boersma 1993 on the STFT's frames: ``jatts_stft_mag`` -> ``jatts_acf_from_mag``, the same exact-f32 MFMA contraction ->
+``jatts_pitch_pick``), pinned on a float64 restatement; parity with DIO / StoneMask is UNPINNED.  The steps after the raw track
+(continuous F0, log, length adjustment, token average) ARE pinned on the real ``Dio.forward`` (``tests/golden/pitch_post_kat.npz``).
 
 The second half of stage 1 lives here too: ``FeatureStatistics`` is the per-feature ``sklearn.preprocessing.StandardScaler`` of
 ``jatts/bin/compute_statistics.py:75-103`` as a running float64 state on the device (``jatts_col_moments``: one launch pair per
@@ -634,3 +639,144 @@ def read_audio(wav_path, sr, start=None, end=None, global_gain_scale=1.0):
     offsets at the file's own rate by truncation (int(offset * sr_native), int(duration * sr_native))."""
     w = read_audio_batch([(wav_path, start, end)], sr, global_gain_scale)[0]
     return None if w is None else w.cpu().numpy()
+
+
+# ---- pitch (csrc/pitch.hip; DESIGN §7 f.8)
+# The estimator is this project's own: Boersma's 1993 autocorrelation method on the STFT's frames (the definition is written out in
+# csrc/pitch.hip and DESIGN §7 f.8), pinned on a float64 restatement (tests/pitch_reference.py).  Parity with the reference's DIO +
+# StoneMask (pyworld, absent from the build environment) is UNPINNED.  The steps after the raw track -- continuous F0, log, length
+# adjustment, token average -- ARE pinned on the real Dio.forward (tests/golden/pitch_post_kat.npz).
+PITCH_VOICING_THRESHOLD, PITCH_SILENCE_THRESHOLD, PITCH_OCTAVE_COST = 0.45, 0.03, 0.01      # Boersma's defaults
+
+
+def pitch_geometry(sr, n_fft, f0min, f0max):
+    """-> (lo, hi, W): the lag range lo = ceil(sr / f0max) .. hi = floor(sr / f0min) and the analysis window's length W = min(3 hi,
+    n_fft - hi - 1) rounded down to even (W + hi < n_fft keeps the circular autocorrelation from wrapping).  ValueError when the
+    window cannot hold two of the longest periods (W < 2 hi) or lo < 2."""
+    if not 0 < f0min < f0max:
+        raise ValueError(f"pitch: 0 < f0min < f0max expected (got {f0min}, {f0max})")
+    lo, hi = int(math.ceil(sr / f0max)), int(math.floor(sr / f0min))
+    w = min(3 * hi, n_fft - hi - 1) // 2 * 2
+    if w < 2 * hi or lo < 2:
+        raise ValueError(f"pitch: f0 range {f0min}-{f0max} Hz at {sr} Hz needs lags {lo}..{hi}, an fft_size of {n_fft} leaves a window of "
+                         f"{max(w, 0)} samples (two periods of f0min and lo >= 2 are needed): raise f0min or fft_size")
+    return lo, hi, w
+
+
+def window_autocorrelation(window_padded, n_lags):
+    """float64 (n_lags,): rw(tau) = sum_n w[n] w[n + tau]"""
+    w = np.asarray(window_padded, dtype=np.float64)
+    return np.array([np.dot(w[:w.size - t], w[t:]) for t in range(n_lags)], dtype=np.float64)
+
+
+def acf_table(window_padded, n_fft, hi):
+    """float32 (K, Lp), K = n_bins rounded up to 64, Lp = hi + 2 rounded up to 32 (what jatts_acf_from_mag takes): entry [k][tau] =
+    c_k cos(2 pi k tau / n_fft) / n_fft * rw(0) / rw(tau), c_0 = c_{n_fft/2} = 1, else 2, for k < n_bins and tau <= hi + 1, zeros in the
+    padding.  Angles are reduced in integers (k tau mod n_fft); the product is taken in float64 and rounded to f32 once."""
+    n_bins = n_fft // 2 + 1
+    k_rows, lp = hip.round_up(n_bins, 64), hip.round_up(hi + 2, 32)
+    rw = window_autocorrelation(window_padded, hi + 2)
+    if not (rw > 0.0).all():
+        raise ValueError("pitch: the window's autocorrelation vanishes inside the lag range")
+    kt = (np.arange(n_bins, dtype=np.int64)[:, None] * np.arange(hi + 2, dtype=np.int64)[None, :]) % n_fft
+    c = np.full(n_bins, 2.0)
+    c[0] = c[-1] = 1.0
+    t = np.zeros((k_rows, lp), dtype=np.float32)
+    t[:n_bins, :hi + 2] = (c[:, None] * np.cos((2.0 * np.pi / n_fft) * kt.astype(np.float64)) / n_fft * (rw[0] / rw)[None, :]).astype(np.float32)
+    return t
+
+
+class Pitch:
+    """``Dio`` of the reference (dio.py:21-159) on the GPU, with the autocorrelation estimator above in place of pyworld: same
+    constructor, ``forward(input, f0min, f0max, feat_length, durations)``: ndarray in, float32 ndarray out.  ``extract`` is the ragged
+    entry over a ``PackedWaves``.  One table pair (windowed DFT, autocorrelation) is kept per (f0min, f0max).  Parity of the raw track
+    with DIO / StoneMask is UNPINNED; everything after it follows ``Dio.forward`` and is pinned on it."""
+
+    def __init__(self, fs=22050, n_fft=1024, hop_length=256, use_token_averaged_f0=True, use_continuous_f0=True, use_log_f0=True,
+                 reduction_factor=None, voicing_threshold=PITCH_VOICING_THRESHOLD, silence_threshold=PITCH_SILENCE_THRESHOLD,
+                 octave_cost=PITCH_OCTAVE_COST, device="cuda"):
+        if use_token_averaged_f0 and not (reduction_factor is not None and reduction_factor >= 1):
+            raise ValueError(f"use_token_averaged_f0 needs reduction_factor >= 1 (got {reduction_factor})")      # dio.py:58-59
+        _check_stft_params(n_fft, hop_length)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _abi.JattsHipError("jatts_amd.features runs on the GPU only (no CPU fallback)")
+        _abi.load()
+        self.fs, self.n_fft, self.hop_length = fs, int(n_fft), int(hop_length)
+        self.use_token_averaged_f0, self.use_continuous_f0, self.use_log_f0 = use_token_averaged_f0, use_continuous_f0, use_log_f0
+        self.reduction_factor = reduction_factor
+        self.voicing_threshold, self.silence_threshold, self.octave_cost = float(voicing_threshold), float(silence_threshold), float(octave_cost)
+        self.ld_mag = hip.round_up(self.n_fft // 2 + 1, 64)
+        self._tables = {}
+
+    def output_size(self):
+        return 1
+
+    def get_parameters(self):
+        return dict(fs=self.fs, n_fft=self.n_fft, hop_length=self.hop_length, use_token_averaged_f0=self.use_token_averaged_f0,
+                    use_continuous_f0=self.use_continuous_f0, use_log_f0=self.use_log_f0, reduction_factor=self.reduction_factor)
+
+    def tables(self, f0min, f0max):
+        """(lo, hi, sum w^2, windowed DFT table, autocorrelation table) of a range, built once."""
+        key = (float(f0min), float(f0max))
+        hit = self._tables.get(key)
+        if hit is None:
+            lo, hi, w_len = pitch_geometry(self.fs, self.n_fft, f0min, f0max)
+            win = padded_window("hann", w_len, self.n_fft)
+            hit = (lo, hi, float(np.dot(win, win)), torch.from_numpy(dft_table(win, self.n_fft)).to(self.device),
+                   torch.from_numpy(acf_table(win, self.n_fft, hi)).to(self.device))
+            self._tables[key] = hit
+        return hit
+
+    @torch.no_grad()
+    def raw(self, waves, f0min, f0max, peaks=None):
+        """Steps 1-5 over a ``PackedWaves`` -> (RaggedBatch over frames, f0 f32 (rows,) with 0 for unvoiced frames, tau int32 (rows,)).
+        ``peaks``: device f32 (n_seq,) max |x| per utterance (default: one ``jatts_wave_gain_peak`` launch with gain 1)."""
+        if not isinstance(waves, PackedWaves):
+            raise TypeError("Pitch.raw takes a PackedWaves")
+        if not waves.lens:
+            raise ValueError("no waveform")
+        lo, hi, sum_w2, dft, acf = self.tables(f0min, f0max)
+        rb = hip.RaggedBatch([frame_count(n, self.n_fft, self.hop_length) for n in waves.lens], self.device)
+        if peaks is None:
+            peak, stride = hip.wave_gain_peak(waves.cu, len(waves.lens), waves.x, 1.0), 2      # (x * 1.0: the samples keep their bits)
+        else:
+            peak, stride = peaks.to(torch.float32).contiguous(), 1
+        mag, _ = hip.stft_mag(rb, waves.cu, waves.lens, waves.x, dft, self.n_fft, self.hop_length, self.ld_mag)
+        r = hip.acf_from_mag(rb, mag, acf)
+        f0, tau = hip.pitch_pick(rb, r, peak, stride, lo, hi, self.fs, f0min, sum_w2, self.voicing_threshold, self.silence_threshold,
+                                 self.octave_cost)
+        return rb, f0, tau
+
+    @torch.no_grad()
+    def post(self, rb, f0, feat_lengths=None, durations=None):
+        """Step 6 on a raw track (dio.py:110-159) -> list of per-utterance f32 device tensors."""
+        p = hip.f0_continuous_log(rb, f0, self.use_continuous_f0, self.use_log_f0)
+        if feat_lengths is not None:
+            if len(feat_lengths) != rb.n_seq or min(int(v) for v in feat_lengths) < 0:
+                raise ValueError("feat_lengths: one non-negative length per utterance")
+            rb_out = hip.RaggedBatch([int(v) for v in feat_lengths], self.device)
+            p, rb = hip.energy_adjust(rb, rb_out, p), rb_out
+        if self.use_token_averaged_f0:
+            if durations is None or len(durations) != rb.n_seq:
+                raise ValueError("use_token_averaged_f0 needs durations: one sequence per utterance")
+            ds = [np.asarray(torch.as_tensor(d).cpu()).astype(np.int64).reshape(-1) * int(self.reduction_factor) for d in durations]
+            cum = []
+            for d, n in zip(ds, rb.lens):
+                if (d < 0).any() or not 0 <= n - int(d.sum()) < self.reduction_factor:
+                    raise ValueError(f"durations sum to {int(d.sum())}, the utterance has {n} frames")      # dio.py:149
+                cum.extend(int(v) for v in np.cumsum(d))
+            rb_tok = hip.RaggedBatch([len(d) for d in ds], self.device)
+            p, rb = hip.token_average(rb_tok, rb, hip.h2d(cum or [0], torch.int32, self.device), p), rb_tok
+        return [p[rb.cu_host[b]:rb.cu_host[b + 1]] for b in range(rb.n_seq)]
+
+    def extract(self, waves, f0min, f0max, feat_lengths=None, durations=None, peaks=None):
+        """The ragged entry: a ``PackedWaves`` of utterances that share one f0 range -> list of per-utterance f32 device tensors."""
+        rb, f0, _ = self.raw(waves, f0min, f0max, peaks)
+        return self.post(rb, f0, feat_lengths, durations)
+
+    def forward(self, input, f0min=80, f0max=400, feat_length=None, durations=None):
+        pw = PackedWaves.from_list([np.asarray(input)], self.device)
+        out = self.extract(pw, f0min, f0max, None if feat_length is None else [int(feat_length)],
+                           [durations] if self.use_token_averaged_f0 else None)
+        return out[0].cpu().numpy()

@@ -1381,6 +1381,61 @@ def wave_gain_peak(cu, n_seq, y, gain):
     return peak
 
 
+# ---- stage-1 pitch (csrc/pitch.hip; host layer: jatts_amd/features.py)
+def acf_from_mag(rb_frames, mag, table, out=None):
+    """jatts_acf_from_mag: mag f32 (rows, ldm >= K) -> r f32 (rows, Lp), r[row][tau] = sum_k mag[row][k]^2 table[k][tau]; ``table``:
+    features.acf_table (K, Lp).  ``out``: a device buffer of at least rows * Lp floats to write into (default: a new one)."""
+    lib = _abi.load()
+    mag, table = _dev(mag), _dev(table)
+    if mag.dtype != torch.float32 or table.dtype != torch.float32 or not mag.is_contiguous() or not table.is_contiguous() \
+            or mag.dim() != 2 or table.dim() != 2:
+        raise ValueError("acf_from_mag: contiguous float32 (rows, ldm) spectra and a (K, Lp) float32 table expected")
+    if mag.shape[0] < rb_frames.total:
+        raise ValueError("acf_from_mag: fewer spectrum rows than frames")
+    k, lp = int(table.shape[0]), int(table.shape[1])
+    if out is None:
+        out = torch.empty(rb_frames.total, lp, dtype=torch.float32, device=mag.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < rb_frames.total * lp:
+        raise ValueError("acf_from_mag: out must be a contiguous float32 device buffer of at least rows * Lp elements")
+    rg = rb_frames.struct()
+    _abi.check(lib.jatts_acf_from_mag(C.byref(rg), mag.data_ptr(), mag.shape[1], table.data_ptr(), k, lp, out.data_ptr(), _stream()),
+               "jatts_acf_from_mag")
+    _count(2.0 * k * lp * rb_frames.total)
+    return out
+
+
+def pitch_pick(rb_frames, r, peak, peak_stride, lo, hi, sr, f0min, sum_w2, voicing_threshold=0.45, silence_threshold=0.03,
+               octave_cost=0.01):
+    """jatts_pitch_pick: r f32 (rows, ldr) -> (f0 f32 (rows,), tau int32 (rows,)).  ``peak``: device f32 with max |x| of utterance b at
+    element b * peak_stride (a view into hip.wave_gain_peak's result has stride 2)."""
+    lib = _abi.load()
+    r, peak = _dev(r), _dev(peak)
+    if r.dtype != torch.float32 or peak.dtype != torch.float32 or r.dim() != 2 or not r.is_contiguous() or r.shape[0] < rb_frames.total:
+        raise ValueError("pitch_pick: contiguous float32 (rows, ldr) autocorrelations and float32 peaks expected")
+    if peak_stride < 1 or peak.numel() < (rb_frames.n_seq - 1) * peak_stride + 1:
+        raise ValueError("pitch_pick: one peak per utterance expected")
+    f0 = torch.empty(rb_frames.total, dtype=torch.float32, device=r.device)
+    tau = torch.empty(rb_frames.total, dtype=torch.int32, device=r.device)
+    rg = rb_frames.struct()
+    _abi.check(lib.jatts_pitch_pick(C.byref(rg), r.data_ptr(), r.shape[1], peak.data_ptr(), int(peak_stride), int(lo), int(hi), float(sr),
+                                    float(f0min), float(sum_w2), float(voicing_threshold), float(silence_threshold), float(octave_cost),
+                                    f0.data_ptr(), tau.data_ptr(), _stream()), "jatts_pitch_pick")
+    return f0, tau
+
+
+def f0_continuous_log(rb_frames, f0, use_continuous=True, use_log=True):
+    """jatts_f0_continuous_log: Dio._convert_to_continuous_f0 and the log of the non-zero values, per utterance -> f32 (rows,)."""
+    lib = _abi.load()
+    f0 = _dev(f0)
+    if f0.dtype != torch.float32 or f0.dim() != 1 or not f0.is_contiguous() or f0.numel() < rb_frames.total:
+        raise ValueError("f0_continuous_log: a contiguous float32 track of the batch's frames expected")
+    out = torch.empty(rb_frames.total, dtype=torch.float32, device=f0.device)
+    rg = rb_frames.struct()
+    _abi.check(lib.jatts_f0_continuous_log(C.byref(rg), f0.data_ptr(), int(bool(use_continuous)), int(bool(use_log)), out.data_ptr(), _stream()),
+               "jatts_f0_continuous_log")
+    return out
+
+
 # ---- stage-1 statistics (csrc/stats.hip; host layer: jatts_amd/features.py)
 def col_moments_ws_doubles(rows, dim):
     """Doubles of workspace a col_moments call over ``rows`` rows needs: two sums per column and group of rows (include/jatts_hip.h)."""
