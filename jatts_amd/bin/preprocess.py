@@ -93,11 +93,9 @@ def _h5_writer():
     return write
 
 
-def _npz_writer():
-    def write(path, entries):
-        with open(path, "wb") as f:
-            np.savez(f, **entries)
-    return write
+def _write_npz(path, entries):
+    with open(path, "wb") as f:
+        np.savez(f, **entries)
 
 
 def _none_if_empty(v):
@@ -135,35 +133,32 @@ def main(argv=None):
     for f in feats:
         if f not in known:
             logging.info(f"Not supported feature type {f}. Skip.")
-    if "energy" in known and any(_none_if_empty(item.get("durations")) is None for item in dataset):
-        raise ValueError("feat_list holds 'energy': every row of the csv needs a durations column (token-averaged energy)")
+    for f, averaged in (("energy", "energy"), ("pitch", "f0")):
+        if f in known and any(_none_if_empty(item.get("durations")) is None for item in dataset):
+            raise ValueError(f"feat_list holds '{f}': every row of the csv needs a durations column (token-averaged {averaged})")
     f0_all = None
-    if "pitch" in known:
-        if any(_none_if_empty(item.get("durations")) is None for item in dataset):
-            raise ValueError("feat_list holds 'pitch': every row of the csv needs a durations column (token-averaged f0)")
-        if args.f0_path is not None:                                         # preprocess.py:94-99
-            with open(args.f0_path) as f:
-                f0_all = yaml.load(f, Loader=yaml.Loader)
-            for item in dataset:
-                if item.get("spk") not in f0_all:
-                    raise KeyError(f"{args.f0_path} has no f0 range for speaker {item.get('spk')!r} ({item.get('sample_id')})")
-    write = _h5_writer() if args.dump_format == "h5" else _npz_writer()
+    if "pitch" in known and args.f0_path is not None:                      # preprocess.py:94-99
+        with open(args.f0_path) as f:
+            f0_all = yaml.load(f, Loader=yaml.Loader)
+        for item in dataset:
+            if item.get("spk") not in f0_all:
+                raise KeyError(f"{args.f0_path} has no f0 range for speaker {item.get('spk')!r} ({item.get('sample_id')})")
+    write = _h5_writer() if args.dump_format == "h5" else _write_npz
     if not dataset:
         raise ValueError(f"{args.csv} lists no utterance")
 
     device = torch.device("cuda")
     sr = config["sampling_rate"]
-    stft = dict(fft_size=config["fft_size"], hop_size=config["hop_size"], win_length=config["win_length"], window=config["window"])
-    mel_ex = features.LogMelExtractor(device, sr, num_mels=config["num_mels"], fmin=config["fmin"], fmax=config["fmax"],
-                                      log_base=config.get("log_base", 10.0), **stft) if "mel" in known else None
-    energy_ex = None
-    if "energy" in known:
-        energy_ex = features.Energy(fs=sr, n_fft=config["fft_size"], win_length=config["win_length"], hop_length=config["hop_size"],
-                                    window=config["window"], use_token_averaged_energy=True,
-                                    reduction_factor=config["model_params"]["reduction_factor"], device=device)
-    pitch_ex = None
+    stft = features.Stft(device, config["fft_size"], config["hop_size"], config["win_length"], config["window"]) \
+        if "mel" in known or "energy" in known else None                      # one front end (one DFT table) serves both
+    ex_mel = features.LogMelExtractor(device, sr, num_mels=config["num_mels"], fmin=config["fmin"], fmax=config["fmax"],
+                                      log_base=config.get("log_base", 10.0), stft=stft) if "mel" in known else None
+    ex_energy = features.Energy(fs=sr, n_fft=config["fft_size"], win_length=config["win_length"], hop_length=config["hop_size"],
+                                window=config["window"], use_token_averaged_energy=True,
+                                reduction_factor=config["model_params"]["reduction_factor"], stft=stft) if "energy" in known else None
+    ex_pitch = None
     if "pitch" in known:
-        pitch_ex = features.Pitch(fs=sr, n_fft=config["fft_size"], hop_length=config["hop_size"], use_token_averaged_f0=True,
+        ex_pitch = features.Pitch(fs=sr, n_fft=config["fft_size"], hop_length=config["hop_size"], use_token_averaged_f0=True,
                                   use_continuous_f0=True, use_log_f0=True, reduction_factor=config["model_params"]["reduction_factor"],
                                   voicing_threshold=config.get("pitch_voicing_threshold", features.PITCH_VOICING_THRESHOLD),
                                   silence_threshold=config.get("pitch_silence_threshold", features.PITCH_SILENCE_THRESHOLD),
@@ -175,10 +170,10 @@ def main(argv=None):
             return config["pitch_extract_f0min"], config["pitch_extract_f0max"]
         for rng in sorted({f0_range(item) for item in dataset}):             # a range the geometry refuses ends the run here
             features.pitch_geometry(sr, config["fft_size"], *rng)
-    spk_ex = None
+    ex_spk = None
     if "spkemb" in known:
         from jatts_amd.spkemb import SpkEmbExtractor
-        spk_ex = SpkEmbExtractor(device, checkpoint=spkemb_checkpoint(config), **config.get("spkemb_params", {}))       # ECAPA_TDNN kwargs
+        ex_spk = SpkEmbExtractor(device, checkpoint=spkemb_checkpoint(config), **config.get("spkemb_params", {}))       # ECAPA_TDNN kwargs
 
     os.makedirs(args.dumpdir, exist_ok=True)
     new_datas = []
@@ -199,11 +194,11 @@ def main(argv=None):
         if _none_if_empty(kept[0][0].get("durations")) is not None:
             durations = [None if _none_if_empty(item.get("durations")) is None else [int(d) for d in item["durations"].split(" ")]
                          for item, _ in kept]
-        pw = features.PackedWaves(torch.cat([w for _, w in kept]).contiguous(), [int(w.numel()) for _, w in kept])
+        pw = features.PackedWaves.from_list([w for _, w in kept], device)
         entries = [{"wave": w.cpu().numpy().astype(np.float32)} for _, w in kept]
-        if mel_ex is not None:
-            rb, mel = mel_ex(pw)
-            mel = mel[:, :mel_ex.num_mels].cpu().numpy()
+        if ex_mel is not None:
+            rb, mel = ex_mel(pw)
+            mel = mel[:, :ex_mel.num_mels].cpu().numpy()
             for i, (item, _) in enumerate(kept):
                 feat = mel[rb.cu_host[i]:rb.cu_host[i + 1]]
                 if durations is not None and durations[i] is not None:      # check duration (preprocess.py:258-261)
@@ -211,23 +206,22 @@ def main(argv=None):
                     assert total == feat.shape[0], \
                         f"{item['sample_id']}: mel duration {feat.shape[0]} and phoneme durations {total} don't match ."
                 entries[i]["mel"] = np.ascontiguousarray(feat, dtype=np.float32)
-        if pitch_ex is not None:
+        if ex_pitch is not None:
             by_range = {}
             for i, (item, _) in enumerate(kept):
                 by_range.setdefault(f0_range(item), []).append(i)
             for (f0min, f0max), members in by_range.items():                 # one ragged run per range, as read_audio_batch groups by rate
-                sub = pw if len(members) == len(kept) else features.PackedWaves(
-                    torch.cat([kept[i][1] for i in members]).contiguous(), [int(kept[i][1].numel()) for i in members])
+                sub = pw if len(members) == len(kept) else pw.select(members)
                 # (feat_length = len(mel), preprocess.py:272-276: the track has the mel's frames already)
-                pit = pitch_ex.extract(sub, f0min, f0max, None, [durations[i] for i in members])
+                pit = ex_pitch.extract(sub, f0min, f0max, None, [durations[i] for i in members])
                 for i, v in zip(members, pit):
                     entries[i]["pitch"] = v.cpu().numpy().astype(np.float32)
-        if energy_ex is not None:
-            en = energy_ex._ex.energy(pw, [sum(d) for d in durations], durations)
+        if ex_energy is not None:
+            en = ex_energy.extract(pw, [sum(d) for d in durations], durations)
             for i, e in enumerate(en):
                 entries[i]["energy"] = e.cpu().numpy().astype(np.float32)
-        if spk_ex is not None:
-            emb = spk_ex.forward_many([item["wav_path"] for item, _ in kept])
+        if ex_spk is not None:
+            emb = ex_spk.forward_many([item["wav_path"] for item, _ in kept])
             for i in range(len(kept)):
                 entries[i]["spkemb"] = np.asarray(emb[i], dtype=np.float32).reshape(-1)
         for (item, _), ent in zip(kept, entries):

@@ -287,6 +287,14 @@ _GEOM_CACHE = {}      # (lens, device) -> (cu tensor, upload-complete event); in
 _GEOM_CACHE_MAX = 512
 
 
+def exclusive_scan(lens):
+    """[0, l0, l0 + l1, ..., sum(lens)]: the offsets of a packed ragged batch (``RaggedBatch.cu_host``, ``features.PackedWaves.cu_host``)."""
+    cu = [0]
+    for v in lens:
+        cu.append(cu[-1] + v)
+    return cu
+
+
 class RaggedBatch:
     """Packed ragged batch geometry: sequence b owns rows cu[b]..cu[b+1]-1.
 
@@ -295,10 +303,7 @@ class RaggedBatch:
 
     def __init__(self, lens, device):
         self.lens = [int(v) for v in lens]
-        cu = [0]
-        for v in self.lens:
-            cu.append(cu[-1] + v)
-        self.cu_host = cu
+        self.cu_host = cu = exclusive_scan(self.lens)
         self.total = cu[-1]
         self.n_seq = len(self.lens)
         self.max_len = max(self.lens) if self.lens else 0
@@ -1276,15 +1281,22 @@ def se_scale_add(rb, x, s, resid=None, out=None, out_col0=0):
     return y
 
 
-# ---- stage-1 features (csrc/features.hip; host layer: jatts_amd/features.py)
+# ---- stage-1 features (csrc/features.hip; host layer: jatts_amd/features/stft.py)
+def _f32d(name, what, *ts, dims=None, numel=0):
+    """Stage-1 operand check: all on the device (JattsHipError), then float32, contiguous, ``dims[i]``-dimensional where given and of at
+    least ``numel`` elements (ValueError)."""
+    ts = [_dev(t) for t in ts]
+    if any(t.dtype != torch.float32 or not t.is_contiguous() or d not in (None, t.dim()) or t.numel() < numel
+           for t, d in zip(ts, dims or [None] * len(ts))):
+        raise ValueError(f"{name}: {what} expected")
+
+
 def stft_mag(rb_frames, cu_samples, n_samples, x, table, n_fft, hop, ldo, want_pow=False):
     """jatts_stft_mag: packed f32 waveforms -> (mag f32 (rows, ldo), pow_sum f32 (rows,) or None).  ``n_samples``: host list of the
     utterance lengths, ``cu_samples``: their exclusive scan on the device, ``table``: features.dft_table.  Geometry the library
     refuses (n_fft, hop, ldo, short utterances) goes through to it for its message."""
     lib = _abi.load()
-    x = _dev(x)
-    if x.dtype != torch.float32 or table.dtype != torch.float32 or not x.is_contiguous() or not table.is_contiguous():
-        raise ValueError("stft_mag: contiguous float32 samples and table expected")
+    _f32d("stft_mag", "contiguous float32 samples and table", x, table)
     if len(n_samples) != rb_frames.n_seq or cu_samples.numel() != rb_frames.n_seq + 1 or x.numel() < sum(n_samples):
         raise ValueError("stft_mag: sample geometry does not match the frame geometry")
     if 64 <= n_fft <= 2048 and table.numel() != n_fft * 2 * round_up(n_fft // 2 + 1, 32):
@@ -1295,7 +1307,7 @@ def stft_mag(rb_frames, cu_samples, n_samples, x, table, n_fft, hop, ldo, want_p
     rg = rb_frames.struct()
     if want_pow:
         _ws(x.device)
-    rc = lib.jatts_stft_mag(C.byref(rg), _dev(cu_samples).data_ptr(), ns, x.data_ptr(), _dev(table).data_ptr(), n_fft, hop,
+    rc = lib.jatts_stft_mag(C.byref(rg), _dev(cu_samples).data_ptr(), ns, x.data_ptr(), table.data_ptr(), n_fft, hop,
                             out.data_ptr(), ldo, _ptr(pw), _stream())
     if want_pow:
         _ws_check(rc, "jatts_stft_mag")
@@ -1340,15 +1352,13 @@ def token_average(rb_tokens, rb_frames, cum, e):
     return out
 
 
-# ---- stage-1 audio reading (csrc/resample.hip; host layer: jatts_amd/features.py)
+# ---- stage-1 audio reading (csrc/resample.hip; host layer: jatts_amd/features/audio.py)
 def resample(cu_in, cu_out, n_in, n_out, x, table, up, down, half_len, out=None):
     """jatts_resample: packed f32 waveforms -> packed f32 waveforms at up / down times the rate.  ``n_in`` / ``n_out``: host lists of the
     utterance lengths (n_out = ceil(n_in * up / down)), ``cu_in`` / ``cu_out``: their exclusive scans on the device, ``table``:
     features.resample_table (K, Nbp).  ``out``: a device buffer of at least sum(n_out) floats to write into (default: a new one)."""
     lib = _abi.load()
-    x, table = _dev(x), _dev(table)
-    if x.dtype != torch.float32 or table.dtype != torch.float32 or not x.is_contiguous() or not table.is_contiguous() or table.dim() != 2:
-        raise ValueError("resample: contiguous float32 samples and a (K, Nbp) float32 table expected")
+    _f32d("resample", "contiguous float32 samples and a (K, Nbp) float32 table", x, table, dims=(None, 2))
     n_in, n_out = [int(v) for v in n_in], [int(v) for v in n_out]
     if len(n_out) != len(n_in) or cu_in.numel() != len(n_in) + 1 or cu_out.numel() != len(n_in) + 1 or x.numel() < sum(n_in):
         raise ValueError("resample: sample geometry does not match the lengths")
@@ -1381,15 +1391,12 @@ def wave_gain_peak(cu, n_seq, y, gain):
     return peak
 
 
-# ---- stage-1 pitch (csrc/pitch.hip; host layer: jatts_amd/features.py)
+# ---- stage-1 pitch (csrc/pitch.hip; host layer: jatts_amd/features/pitch.py)
 def acf_from_mag(rb_frames, mag, table, out=None):
     """jatts_acf_from_mag: mag f32 (rows, ldm >= K) -> r f32 (rows, Lp), r[row][tau] = sum_k mag[row][k]^2 table[k][tau]; ``table``:
     features.acf_table (K, Lp).  ``out``: a device buffer of at least rows * Lp floats to write into (default: a new one)."""
     lib = _abi.load()
-    mag, table = _dev(mag), _dev(table)
-    if mag.dtype != torch.float32 or table.dtype != torch.float32 or not mag.is_contiguous() or not table.is_contiguous() \
-            or mag.dim() != 2 or table.dim() != 2:
-        raise ValueError("acf_from_mag: contiguous float32 (rows, ldm) spectra and a (K, Lp) float32 table expected")
+    _f32d("acf_from_mag", "contiguous float32 (rows, ldm) spectra and a (K, Lp) float32 table", mag, table, dims=(2, 2))
     if mag.shape[0] < rb_frames.total:
         raise ValueError("acf_from_mag: fewer spectrum rows than frames")
     k, lp = int(table.shape[0]), int(table.shape[1])
@@ -1426,9 +1433,7 @@ def pitch_pick(rb_frames, r, peak, peak_stride, lo, hi, sr, f0min, sum_w2, voici
 def f0_continuous_log(rb_frames, f0, use_continuous=True, use_log=True):
     """jatts_f0_continuous_log: Dio._convert_to_continuous_f0 and the log of the non-zero values, per utterance -> f32 (rows,)."""
     lib = _abi.load()
-    f0 = _dev(f0)
-    if f0.dtype != torch.float32 or f0.dim() != 1 or not f0.is_contiguous() or f0.numel() < rb_frames.total:
-        raise ValueError("f0_continuous_log: a contiguous float32 track of the batch's frames expected")
+    _f32d("f0_continuous_log", "a contiguous float32 track of the batch's frames", f0, dims=(1,), numel=rb_frames.total)
     out = torch.empty(rb_frames.total, dtype=torch.float32, device=f0.device)
     rg = rb_frames.struct()
     _abi.check(lib.jatts_f0_continuous_log(C.byref(rg), f0.data_ptr(), int(bool(use_continuous)), int(bool(use_log)), out.data_ptr(), _stream()),
@@ -1436,7 +1441,7 @@ def f0_continuous_log(rb_frames, f0, use_continuous=True, use_log=True):
     return out
 
 
-# ---- stage-1 statistics (csrc/stats.hip; host layer: jatts_amd/features.py)
+# ---- stage-1 statistics (csrc/stats.hip; host layer: jatts_amd/features/stats.py)
 def col_moments_ws_doubles(rows, dim):
     """Doubles of workspace a col_moments call over ``rows`` rows needs: two sums per column and group of rows (include/jatts_hip.h)."""
     return -(-int(rows) // _abi.STATS_ROWS_PER_GROUP) * 2 * int(dim) if rows > 0 else 0
@@ -1446,9 +1451,8 @@ def col_moments(x, ld, dim, rows, state, ws):
     """jatts_col_moments: one partial_fit of the f32 matrix x[rows][ld] (first ``dim`` columns) into ``state`` (float64 (3, dim):
     n | mean | M2) through the caller's float64 workspace ``ws``.  Asynchronous, reads nothing back."""
     lib = _abi.load()
-    x, state, ws = _dev(x), _dev(state), _dev(ws)
-    if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < rows * ld:
-        raise ValueError("col_moments: contiguous float32 (rows, ld) expected")
+    _f32d("col_moments", "contiguous float32 (rows, ld)", x, numel=rows * ld)
+    state, ws = _dev(state), _dev(ws)
     if state.dtype != torch.float64 or ws.dtype != torch.float64 or not state.is_contiguous() or state.numel() != 3 * dim:
         raise ValueError("col_moments: state is float64 (3, dim), the workspace float64")
     _abi.check(lib.jatts_col_moments(x.data_ptr(), ld, dim, rows, state.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "jatts_col_moments")
@@ -1470,9 +1474,8 @@ def col_moments_merge(state, other):
 def standardize(x, mean, scale, dim, ldy=None):
     """jatts_standardize: (x - mean) / scale on the first ``dim`` columns of f32 x (rows, ld), zeros up to ``ldy`` (default: x's ld)."""
     lib = _abi.load()
-    x, mean, scale = _dev(x), _dev(mean), _dev(scale)
-    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
-        raise ValueError("standardize: contiguous float32 (rows, ld) expected")
+    _f32d("standardize", "contiguous float32 (rows, ld)", x, dims=(2,))
+    mean, scale = _dev(mean), _dev(scale)
     if mean.dtype != torch.float32 or scale.dtype != torch.float32 or mean.numel() < dim or scale.numel() < dim \
             or not mean.is_contiguous() or not scale.is_contiguous():
         raise ValueError("standardize: mean / scale are contiguous float32 with at least dim elements")

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .features.common import PackedWaves, require_cuda
 from .wavio import decode_wav
 from .hip import ACT_NONE, ACT_RELU, ACT_TANH
 from .models import _schema as S
@@ -76,9 +77,7 @@ class ECAPA_TDNN(torch.nn.Module):
         return super()._apply(fn, *a, **k)
 
     def _prepare(self):
-        dev = self.fc.conv.weight.device
-        if dev.type != "cuda":
-            raise hip._abi.JattsHipError("jatts_amd ECAPA_TDNN runs on the GPU only (no CPU fallback)")
+        dev = require_cuda(self.fc.conv.weight.device, "jatts_amd ECAPA_TDNN")
         if self._prep is not None and self._prep["dev"] == dev:
             return self._prep
         hip._abi.load()
@@ -193,16 +192,11 @@ class FbankFrontEnd:
     @torch.no_grad()
     def __call__(self, waves):
         """waves: list of 1-D float tensors -> (RaggedBatch over frames, feats f32 (rows, ldo))."""
-        dev = self.window.device
-        ns = [int(w.numel()) for w in waves]
-        if min(ns) < 1:
+        if min(int(w.numel()) for w in waves) < 1:
             raise ValueError("empty waveform")
-        x = torch.cat([w.reshape(-1).float() for w in waves]).to(dev).contiguous()
-        cu = [0]
-        for n in ns:
-            cu.append(cu[-1] + n)
-        rb = hip.RaggedBatch([1 + n // self.hop for n in ns], dev)
-        frames = hip.frame_signal(rb, hip.h2d(cu, torch.int32, dev), x, self.window, self.n_fft, self.hop, self.ldf)
+        pw = PackedWaves.from_list(waves, self.window.device)
+        rb = hip.RaggedBatch([1 + n // self.hop for n in pw.lens], pw.x.device)
+        frames = hip.frame_signal(rb, pw.cu, pw.x, self.window, self.n_fft, self.hop, self.ldf)
         spec = hip.conv1d(rb, frames, self.dft.w, self.dft.c_in, 2 * self.nbp, 1, dtype=F32)            # [re | im]
         power = hip.power_spectrum(spec, self.nbp, self.ldp)
         mel = hip.conv1d(rb, power, self.mel.w, self.mel.c_in, self.n_mels, 1, dtype=F32)
@@ -222,9 +216,7 @@ class SpkEmbExtractor:
     dict (path or dict); results are cached per path."""
 
     def __init__(self, device="cuda", checkpoint=None, **ecapa_kwargs):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise hip._abi.JattsHipError("jatts_amd.SpkEmbExtractor runs on the GPU only (no CPU fallback)")
+        self.device = require_cuda(device, "jatts_amd.SpkEmbExtractor")
         self.model = ECAPA_TDNN(**ecapa_kwargs)
         if checkpoint is not None:
             self.model.load_state_dict(torch.load(checkpoint, map_location="cpu") if not isinstance(checkpoint, dict) else checkpoint)

@@ -120,3 +120,42 @@ def test_cpu_device_raises_jatts_hip_error(lib):
     with pytest.raises(_abi.JattsHipError):     # a CPU tensor at the wrapper
         hip.stft_mag(hip.RaggedBatch([4], "cpu"), torch.tensor([0, 1025], dtype=torch.int32), [1025], torch.zeros(1025),
                      torch.zeros(2048, 2 * 1056), 2048, 300, 1088)
+
+
+# ---- the shared token-average path (features/common.py)
+def test_token_spans_at_reduction_factor_1_wants_the_exact_sum():
+    assert features.token_spans([[3, 0, 4]], [7], 1) == ([3], [3, 3, 7])
+    for n in (6, 8):                                                          # the sum is off by +1 / -1
+        with pytest.raises(ValueError, match=f"durations sum to 7, the utterance has {n} frames"):
+            features.token_spans([[3, 0, 4]], [n], 1)
+
+
+def test_token_spans_at_reduction_factor_2_allows_a_remainder_below_it():
+    for n in (14, 15):                                                        # remainders 0 and 1
+        assert features.token_spans([[3, 0, 4]], [n], 2) == ([3], [6, 6, 14])
+    for n in (16, 13):                                                        # remainder 2, remainder -1
+        with pytest.raises(ValueError, match=f"durations sum to 14, the utterance has {n} frames"):
+            features.token_spans([[3, 0, 4]], [n], 2)
+
+
+def test_token_spans_refusals_and_layout():
+    with pytest.raises(ValueError, match="durations sum to"):
+        features.token_spans([[5, -1, 3]], [7])                               # a negative duration, although the sum fits
+    with pytest.raises(ValueError, match="one sequence per utterance"):
+        features.token_spans([[7]], [7, 7])
+    rng = np.random.default_rng(0)
+    durs = [rng.integers(0, 5, size=n) for n in (1, 9, 4)] + [np.zeros(0, dtype=np.int64)]
+    for rf, extra in ((1, [0, 0, 0, 0]), (3, [2, 0, 1, 0])):
+        lens = [int(d.sum()) * rf + e for d, e in zip(durs, extra)]
+        token_lens, cum = features.token_spans([torch.from_numpy(durs[0]), durs[1].tolist(), durs[2], durs[3]], lens, rf)
+        assert token_lens == [d.size for d in durs]
+        assert cum == np.concatenate([np.cumsum(d * rf) for d in durs]).tolist() and all(type(v) is int for v in cum)
+
+
+def test_every_stage1_name_resolves_on_the_package():
+    names = """LogMelExtractor logmelfilterbank Energy mel_filterbank padded_window dft_table frame_count frame_indices reflect_index
+        FeatureStatistics STATS_ROWS_PER_GROUP stats_from_state save_stats standardize PackedWaves Resampler resample resample_ratio
+        resample_taps resample_design resample_out_len resample_geometry resample_table RESAMPLE_ZEROS RESAMPLE_ROLLOFF RESAMPLE_BETA
+        RESAMPLE_MAX_K RESAMPLE_MAX_NBP RESAMPLE_MAX_TABLE_BYTES seconds_to_samples read_audio read_audio_batch Pitch pitch_geometry
+        window_autocorrelation acf_table PITCH_VOICING_THRESHOLD PITCH_SILENCE_THRESHOLD PITCH_OCTAVE_COST Stft token_spans""".split()
+    assert [n for n in names if not hasattr(features, n)] == []

@@ -235,7 +235,7 @@ def test_other_tile_paths_against_float64(cuda, n_fft, hop, win):
     rng = np.random.default_rng(n_fft)
     waves = [rng.standard_normal(n).astype(np.float32) for n in (101 * hop - 1, 72 * hop, n_fft // 2 + 1, 64 * hop - 1)]
     ex = features.LogMelExtractor(cuda, 16000, fft_size=n_fft, hop_size=hop, win_length=win, num_mels=20)
-    rb, mag, pw = ex._stft(waves, True)
+    rb, mag, pw = ex.stft.magnitude(features.PackedWaves.from_list(waves, cuda), True)
     assert rb.lens == [101, 73, 1 + (n_fft // 2 + 1) // hop, 64]
     nb = n_fft // 2 + 1
     assert tuple(mag.shape) == (rb.total, hip.round_up(nb, 64)) and not mag[:, nb:].any()
@@ -256,3 +256,55 @@ def test_other_tile_paths_against_float64(cuda, n_fft, hop, win):
         e = hip.energy_frames(pw)[rb.cu_host[i]:rb.cu_host[i + 1]].double().cpu().numpy()
         assert (np.abs(e - e64) <= dp / (2 * e64) * 1.01 + 2 * u * e64).all(), i
     print(f"features[n_fft {n_fft}]: worst |error| / bound {worst:.3f}")
+
+
+# ---- one wave packing, one STFT front end, one post path: every entry gives the same bits
+def _three(n_fft):
+    """n_fft // 2 + 1 samples (the shortest reflect padding admits), 1000 and 4097.  At n_fft 2048 reflect padding refuses 1000 samples
+    (1000 <= 1024, asserted by the caller), so 2000 stand in for them there."""
+    rng = np.random.default_rng(n_fft)
+    return [rng.standard_normal(n).astype(np.float32) for n in (n_fft // 2 + 1, 1000 if n_fft < 2000 else 2000, 4097)]
+
+
+@pytest.mark.parametrize("n_fft,hop", [(64, 7), (2048, 300)])
+def test_the_three_input_forms_and_select_give_the_same_bits(cuda, n_fft, hop):
+    from jatts_amd import features
+    ex = features.LogMelExtractor(cuda, 16000, fft_size=n_fft, hop_size=hop, num_mels=20)
+    waves = _three(n_fft)
+    if n_fft == 2048:
+        with pytest.raises(ValueError, match="too short to be reflect-padded"):
+            ex([np.zeros(1000, dtype=np.float32)])
+    pw = features.PackedWaves.from_list(waves, cuda)
+    forms = [waves, [torch.from_numpy(w).to(cuda) for w in waves], pw]
+    mel, feats, en = zip(*[(ex.mel(f), ex(f), ex.energy(f)) for f in forms])
+    for k in (1, 2):
+        assert mel[k][0].lens == mel[0][0].lens == feats[k][0].lens == [1 + len(w) // hop for w in waves]
+        assert torch.equal(mel[k][1], mel[0][1]) and torch.equal(feats[k][1], feats[0][1])
+        assert len(en[k]) == 3 and all(torch.equal(a, b) for a, b in zip(en[k], en[0]))
+    assert feats[0][1].abs().sum() > 0 and all(e.abs().sum() > 0 for e in en[0])          # the comparison is not one of zeros
+    sel, direct = pw.select([2, 0]), features.PackedWaves.from_list([waves[2], waves[0]], cuda)
+    assert sel.lens == direct.lens == [4097, n_fft // 2 + 1] and sel.cu_host == direct.cu_host
+    assert torch.equal(sel.x, direct.x) and torch.equal(sel.cu, direct.cu)
+    rb, full = feats[0]
+    rb_s, got = ex(sel)
+    assert rb_s.lens == [rb.lens[2], rb.lens[0]]
+    assert torch.equal(got, torch.cat([full[rb.cu_host[2]:rb.cu_host[3]], full[rb.cu_host[0]:rb.cu_host[1]]]))
+    with pytest.raises(ValueError, match="no waveform"):
+        features.PackedWaves.from_list([], cuda)
+
+
+def test_the_three_energy_entries_give_the_same_bits(cuda):
+    from jatts_amd import features
+    n_fft, hop = 1024, 256
+    waves = _three(n_fft)
+    frames = [1 + len(w) // hop for w in waves]
+    durs = [[3, 0, n - 3] for n in frames]
+    en = features.Energy(fs=22050, n_fft=n_fft, hop_length=hop, use_token_averaged_energy=True, reduction_factor=1, device=cuda)
+    assert getattr(en, "mel_w", None) is None and getattr(en.stft, "mel_w", None) is None         # a front end, no mel weights
+    ex = features.LogMelExtractor(cuda, 22050, fft_size=n_fft, hop_size=hop)
+    pw = features.PackedWaves.from_list(waves, cuda)
+    ragged, by_mel = en.extract(pw, frames, durs), ex.energy(pw, frames, durs)
+    for i, w in enumerate(waves):
+        one = en.forward(w, frames[i], durs[i])
+        assert one.dtype == np.float32 and one.shape == (3,) and one[1] == 0 and one[0] > 0
+        assert torch.equal(torch.from_numpy(one), ragged[i].cpu()) and torch.equal(ragged[i], by_mel[i]), i

@@ -115,12 +115,11 @@ def test_batch_invariance_of_all_three_kernels(cuda, lib):
 
     def run(ws):
         pw = features.PackedWaves.from_list(ws, cuda)
-        lo, hi, sum_w2, dft, acf = ex.tables(F0MIN, F0MAX)
-        rb = hip.RaggedBatch([features.frame_count(n, n_fft, hop) for n in pw.lens], cuda)
+        t = ex.tables(F0MIN, F0MAX)
         peak = hip.wave_gain_peak(pw.cu, len(pw.lens), pw.x, 1.0)
-        mag, _ = hip.stft_mag(rb, pw.cu, pw.lens, pw.x, dft, n_fft, hop, ex.ld_mag)
-        r = hip.acf_from_mag(rb, mag, acf)
-        f0, tau = hip.pitch_pick(rb, r, peak, 2, lo, hi, sr, F0MIN, sum_w2)
+        rb, mag, _ = t.stft.magnitude(pw)
+        r = hip.acf_from_mag(rb, mag, t.acf)
+        f0, tau = hip.pitch_pick(rb, r, peak, 2, t.lo, t.hi, sr, F0MIN, t.sum_w2)
         p = hip.f0_continuous_log(rb, f0)
         return rb, [t.cpu().numpy() for t in (r, f0, tau, p)]
 

@@ -2,7 +2,7 @@
 """Times the STFT of the feature extractor at the bench batch geometry: 64 utterances x 230 400 samples at 24 kHz, n_fft 2048, hop 300
 (769 frames each).
 
-  leg A  jatts_stft_mag: frames from the waveform inside the kernel, magnitude out (jatts_amd/features.py).
+  leg A  jatts_stft_mag: frames from the waveform inside the kernel, magnitude out (jatts_amd/features/stft.py).
   leg B  the entry points FbankFrontEnd composes, at n_fft 2048: jatts_frame_signal -> jatts_conv1d (DFT as a k = 1 conv, exact f32)
          -> jatts_power_spectrum.  Zero padding and a power spectrum: for TIMING and footprint only.
 
@@ -67,7 +67,7 @@ def main():
     del w, ang
 
     def leg_a():
-        return hip.stft_mag(rb, cu, ns, x, ex.table, n_fft, hop, ex.ld_mag)[0]
+        return hip.stft_mag(rb, cu, ns, x, ex.stft.table, n_fft, hop, ex.stft.ld_mag)[0]
 
     def leg_b():
         frames = hip.frame_signal(rb, cu, x, win, n_fft, hop, n_fft)

@@ -41,7 +41,7 @@ def main():
     sr, n_fft, hop, f0min, f0max = 24000, 2048, 300, 70, 400
     samples = (a.frames - 1) * hop
     ex = features.Pitch(fs=sr, n_fft=n_fft, hop_length=hop, use_token_averaged_f0=False, device=dev)
-    lo, hi, sum_w2, dft, acf = ex.tables(f0min, f0max)
+    lo, hi, sum_w2, front, acf = ex.tables(f0min, f0max)
     w_len = features.pitch_geometry(sr, n_fft, f0min, f0max)[2]
     g = torch.Generator().manual_seed(0)
     t = torch.arange(samples, dtype=torch.float64) / sr
@@ -57,7 +57,7 @@ def main():
     peak = hip.wave_gain_peak(pw.cu, a.utts, pw.x, 1.0)
 
     def stft():
-        return hip.stft_mag(rb, pw.cu, pw.lens, pw.x, dft, n_fft, hop, ex.ld_mag)[0]
+        return front.magnitude(pw)[1]
     mag = stft()
     r = hip.acf_from_mag(rb, mag, acf)
     f0, _ = hip.pitch_pick(rb, r, peak, 2, lo, hi, sr, f0min, sum_w2)
