@@ -1,7 +1,11 @@
-"""Randomised check of jatts_relpos_attention against float64 attention: random ragged lengths (1 .. 330, so every partial-tile and
-one-row case comes up), every d_k the kernel has, legacy / new rel-pos bias or none, with and without the u . k term, aligned and
+"""Randomised check of jatts_relpos_attention against float64 attention: random ragged lengths (1 .. 330, half of them drawn from a list of
+tile-edge values), every d_k the kernel has, legacy / new rel-pos bias or none, with and without the u . k term, aligned and
 element-aligned V^T (NaN in every slack column), key lengths shorter than the padded length (kv_len: the reference's training-time
-forward() on a padded batch, attention.py:80-88), f32 / split / f16.  Complements the fixed cases of test_kernels_gpu.py."""
+forward() on a padded batch, attention.py:80-88), f32 / split / f16.  Which combinations come up is left to the six random streams: replayed
+on the CPU, this file and test_attn_emul_gpu.py together reach 163 of the 192 (arithmetic, d_k, bias form, V^T path) combinations, never run
+the 512-thread split d_k 256 kernel with kv_len or without a rel bias, and measure one global max |out - ref| / max |ref| per case.  The
+branch-by-branch table with bit-exact and elementwise criteria is test_attention_cases_gpu.py (attention_cases.py; profiles/attention_cases.txt).
+Complements the fixed cases of test_kernels_gpu.py."""
 import math
 import random
 
