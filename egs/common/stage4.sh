@@ -14,7 +14,9 @@ stage4_decode() {
     # stats: the reference writes stats.h5 (compute_statistics.py:94-103).  Hosts without h5py read the .npz twin that
     # tools/h5stats_to_npz.py makes on a machine that has it.
     local stats="${expdir}/stats.h5"
-    if ! "${python}" -c 'import h5py' 2>/dev/null; then
+    if [ ! -e "${stats}" ] && [ -e "${expdir}/stats.npz" ]; then
+        stats="${expdir}/stats.npz"      # trained here (egs/common/stage3.sh): stage 1's statistics are .npz
+    elif ! "${python}" -c 'import h5py' 2>/dev/null; then
         if [ -e "${expdir}/stats.npz" ]; then stats="${expdir}/stats.npz"
         else log "h5py is not installed and ${expdir}/stats.npz does not exist: run tools/h5stats_to_npz.py ${expdir}/stats.h5 where h5py is available"; exit 1; fi
     fi

@@ -1,9 +1,10 @@
 #!/usr/bin/env bash
 # egs/hificaptain_jp_female/tts1 (Hi-Fi-CAPTAIN ja-JP female, single speaker) on the MI355X path: the reference recipe's interface (same variables, same --option syntax, same directory
 # layout: exp/<expname>/{config.yml,stats.h5,tokens.txt,*.pkl} -> exp/<expname>/results/<checkpoint>/<set>/wav/*.wav) with
-# stage 1 (feature extraction and statistics, egs/common/stage1.sh) and stage 4 (network decoding) running on jatts_amd.  Stages
-# -1, 0 (download, data preparation), 2, 3 (token list, training) and 5 (evaluation) are the reference's and are not rebuilt here:
-# run them there, then point --expdir / --checkpoint at the result, or start this script inside the reference's recipe directory.
+# stage 1 (feature extraction and statistics, egs/common/stage1.sh), stages 2 and 3 (token list and training, egs/common/stage3.sh) and stage 4
+# (network decoding, egs/common/stage4.sh) running on jatts_amd.  Stages -1, 0 (download, data preparation) and 5 (evaluation) are the reference's
+# and are not rebuilt here: run them there, or start this script inside the reference's recipe directory.
+#     ./run.sh --stage 2 --stop_stage 3 [--conf conf/fastspeech2.v1.yaml] [--tag mytag] [--resume exp/.../checkpoint-10000steps.pkl] [--n_gpus 8]
 #     ./run.sh --stage 1 --stop_stage 1 [--conf conf/matcha_tts.mas.v1.yaml] [--dumpdir dump]
 #     ./run.sh --stage 4 --stop_stage 4 --tag mytag [--checkpoint exp/.../checkpoint-100000steps.pkl] [--n_gpus 8]
 
@@ -35,9 +36,18 @@ token_type="phn"
 token_column="phonemes"
 g2p=julius
 cleaner=none
+oov="<unk>"            # Out of vocabulary symbol.
+blank="<blank>"        # CTC blank symbol.
+sos_eos="<sos/eos>"    # sos and eos symbols.
+nlsyms_txt=none        # Non-linguistic symbol list (needed if existing).
 
 # training related setting
 tag=""         # tag for directory to save model
+resume=""      # checkpoint path to resume training (e.g. <path>/<to>/checkpoint-10000steps.pkl)
+train_precision=""    # the trainers' arithmetic (fp32 when empty; fp32_bf16x3 = f32 tensors, f32-equivalent emulated MFMA operands)
+attention_precision="${attention_precision:-}"  # arithmetic of the attention products in training and decoding (fp32 | fp32_bf16x3; what the precision means when empty)
+train_seed="${train_seed:-}"         # seed of the initial parameters and the shuffle (unseeded when empty, as the reference)
+resident_gb="${resident_gb:-}"        # largest training set, in GiB, kept resident on the device (64 when empty)
 expdir=""      # exp/<expname>; derived from conf / tag like the reference when empty
 
 # decoding related setting
@@ -51,6 +61,7 @@ master_port=29517
 # shellcheck disable=SC1091
 . "${REPO_ROOT}/egs/common/parse_options.sh" || exit 1
 . "${REPO_ROOT}/egs/common/stage1.sh" || exit 1
+. "${REPO_ROOT}/egs/common/stage3.sh" || exit 1
 . "${REPO_ROOT}/egs/common/stage4.sh" || exit 1
 
 set -euo pipefail
@@ -78,8 +89,14 @@ if [ "${stage}" -le 1 ] && [ "${stop_stage}" -ge 1 ]; then
     stage1_features
 fi
 
-if [ "${stage}" -le 3 ] && [ "${stop_stage}" -ge 2 ]; then
-    log "Stages 2 and 3 (token list generation, training) are the reference recipe's own: run them there."
+if [ "${stage}" -le 2 ] && [ "${stop_stage}" -ge 2 ]; then
+    log "Stage 2: Token list generation"
+    stage2_tokens
+fi
+
+if [ "${stage}" -le 3 ] && [ "${stop_stage}" -ge 3 ]; then
+    log "Stage 3: Network training"
+    stage3_train
 fi
 
 if [ "${stage}" -le 4 ] && [ "${stop_stage}" -ge 4 ]; then

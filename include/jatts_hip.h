@@ -784,6 +784,36 @@ int jatts_standardize(const float* x, int32_t ldx, int32_t dim, int64_t rows, co
                       int32_t ldy, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Stage-3 batch assembly (additive to ABI 7, no bump: no descriptor or existing signature changed, and a library without
+ * the symbol is refused when _abi.load binds it).  Replaces, for one training batch, the per-utterance feature read and
+ * StandardScaler.transform of jatts/datasets/tts_dataset.py:69-145 (done once, at load time, by jatts_amd.data.ResidentDataset), the
+ * padding of jatts/collaters/fastspeech2.py:17-107 (pad_list on the CPU) and the `.to(self.device)` copies of
+ * jatts/trainers/fastspeech2.py:24-43: every feature of the training set sits on the device as one flat store, and a batch is ONE
+ * gather launch over all its fields.
+ *   dst[b][t][c] = src[(row_start[u] + t) * dim + c]   for t < row_len[u], u = utt[b];   all-zero bits for t >= row_len[u].
+ * Every element of every dst is written (the caller does not memset).  The copy moves bits: -0.0 and NaN payloads survive.  Padding is
+ * stored as zero, not masked: nothing behind the utterance in the store reaches dst.  Up to JATTS_COLLATE_MAX_FIELDS fields of
+ * different t_max, dim and elem_bytes share the launch; the table travels by value in the kernel arguments (`fields` is HOST memory,
+ * read before the call returns).  16-byte accesses where a slot's source and destination both start on 16 bytes, 4-byte ones elsewhere.
+ * The ids in utt and row_len[u] <= t_max are the CALLER's to check (jatts_amd.hip.collate does, from its host copy of the index); a
+ * row_len above t_max is clamped, so dst is never overrun.
+ * JATTS_ERR_ARG: n_fields outside 1..JATTS_COLLATE_MAX_FIELDS, n_batch < 1, dim < 1, t_max < 1, elem_bytes not 4 or 8, a null pointer,
+ * src / dst not aligned to elem_bytes.  JATTS_ERR_UNSUPPORTED: a slot of 2^31 or more 32-bit words, 2^31 or more workgroups.
+ * ------------------------------------------------------------------------------- */
+#define JATTS_COLLATE_MAX_FIELDS 8
+typedef struct jatts_collate_field {
+  const void* src; /* resident store [total_rows][dim], row-major, no row padding (device) */
+  const int64_t* row_start; /* [n_utt] first row of each utterance in src (device, resident) */
+  const int32_t* row_len; /* [n_utt] rows of each utterance (device, resident) */
+  void* dst; /* [n_batch][t_max][dim] */
+  int32_t elem_bytes; /* 4 (f32) or 8 (i64) */
+  int32_t dim;
+  int32_t t_max;
+} jatts_collate_field;
+int jatts_collate(const jatts_collate_field* fields, int32_t n_fields, const int32_t* utt /* [n_batch] utterance ids, device */,
+                  int32_t n_batch, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Length regulator (modules/length_regulator.py:70-97), bit-exact integer path.
  * Step 1: d_eff = (alpha == 1) ? d : (int64) rint((float)d * alpha)   [half-to-even],
  *         cum[row] = inclusive prefix sum of d_eff inside each sequence, olens[b] = total.

@@ -66,6 +66,14 @@ class RelAttnDesc(C.Structure):
     ]
 
 
+COLLATE_MAX_FIELDS = 8      # JATTS_COLLATE_MAX_FIELDS
+
+
+class CollateField(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("row_start", C.c_void_p), ("row_len", C.c_void_p), ("dst", C.c_void_p),
+                ("elem_bytes", C.c_int32), ("dim", C.c_int32), ("t_max", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/jatts_hip.h declares
 PROTOTYPES = {
     "jatts_abi_version": (C.c_int, []),
@@ -155,6 +163,7 @@ PROTOTYPES = {
     "jatts_col_moments": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "jatts_col_moments_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "jatts_standardize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "jatts_collate": (C.c_int, [C.POINTER(CollateField), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "jatts_seq_mean_std": (C.c_int, [C.POINTER(Ragged), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "jatts_seq_affine_act": (C.c_int, [C.POINTER(Ragged), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,

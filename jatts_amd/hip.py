@@ -1486,6 +1486,85 @@ def standardize(x, mean, scale, dim, ldy=None):
     return y
 
 
+# ---- stage-3 batch assembly (csrc/collate.hip; host layer: jatts_amd/data.py)
+class CollateSource:
+    """One resident feature store for ``collate``: ``src`` (total_rows, dim) float32 or int64 on the device, contiguous, all utterances one behind
+    the other; ``row_start`` / ``row_len``: the per-utterance index as numpy arrays (the host twin, what ``collate`` checks a batch against) and,
+    uploaded once, as int64 / int32 device tensors (what the kernel reads)."""
+
+    def __init__(self, src, row_start, row_len):
+        import numpy as np
+        self.src = _dev(src)
+        self.row_start_host = np.ascontiguousarray(row_start, dtype=np.int64)
+        self.row_len_host = np.ascontiguousarray(row_len, dtype=np.int32)
+        if self.row_start_host.ndim != 1 or self.row_start_host.shape != self.row_len_host.shape:
+            raise ValueError("CollateSource: row_start and row_len are 1-D and of one length")
+        self.n_utt = int(self.row_len_host.shape[0])
+        self.row_start = torch.from_numpy(self.row_start_host).to(src.device)
+        self.row_len = torch.from_numpy(self.row_len_host).to(src.device)
+
+
+def collate(sources, ids, t_max=None, utt=None, out=None):
+    """jatts_collate: one launch that gathers the utterances ``ids`` (a host sequence of ints) out of every CollateSource of ``sources`` into
+    freshly allocated padded batches -> list of (len(ids), t_max, dim) tensors, zero bits behind each utterance's rows.  ``t_max``: one value per
+    source, default the longest member's rows.  ``utt``: ``ids`` as an int32 device tensor when the caller has staged it already.  ``out``: one destination per source to
+    write into instead of allocating (contiguous, (len(ids), t_max, dim), the store's dtype and device; every element is overwritten).  Everything the
+    kernel trusts is checked here against the host index, before any launch: ValueError."""
+    import numpy as np
+    lib = _abi.load()
+    n_f = len(sources)
+    if not 1 <= n_f <= _abi.COLLATE_MAX_FIELDS:
+        raise ValueError(f"collate: {n_f} fields, 1..{_abi.COLLATE_MAX_FIELDS} (JATTS_COLLATE_MAX_FIELDS) go into one launch")
+    idx = np.asarray(ids, dtype=np.int64)
+    if idx.ndim != 1 or idx.size < 1:
+        raise ValueError("collate: ids is a non-empty 1-D sequence of utterance numbers")
+    B = int(idx.size)
+    t_max = [None] * n_f if t_max is None else list(t_max)
+    if len(t_max) != n_f:
+        raise ValueError("collate: one t_max per source")
+    if out is not None and len(out) != n_f:
+        raise ValueError("collate: one out tensor per source")
+    tab = (_abi.CollateField * n_f)()
+    outs = []
+    for i, s in enumerate(sources):
+        src = s.src
+        eb = {torch.float32: 4, torch.int64: 8}.get(src.dtype)
+        if eb is None:
+            raise ValueError(f"collate: a store of {src.dtype} (elem_bytes {src.element_size()}): float32 (4) or int64 (8)")
+        if src.dim() != 2 or not src.is_contiguous():
+            raise ValueError("collate: a store is a contiguous (total_rows, dim) tensor")
+        dim = int(src.shape[1])
+        if dim < 1:
+            raise ValueError("collate: dim < 1")
+        if int(idx.min()) < 0 or int(idx.max()) >= s.n_utt:
+            raise ValueError(f"collate: utterance id outside 0..{s.n_utt - 1}")
+        lens = s.row_len_host[idx]
+        starts = s.row_start_host[idx]
+        if int(lens.min()) < 0 or int(starts.min()) < 0 or int((starts + lens).max()) > src.shape[0]:
+            raise ValueError("collate: the index points outside the store")
+        tm = int(lens.max()) if t_max[i] is None else int(t_max[i])
+        if tm < 1:
+            raise ValueError("collate: t_max < 1")
+        if tm < int(lens.max()):
+            raise ValueError(f"collate: t_max {tm} below a member's {int(lens.max())} rows")
+        if src.device != sources[0].src.device:
+            raise ValueError("collate: stores on different devices")
+        if out is None:
+            dst = torch.empty(B, tm, dim, dtype=src.dtype, device=src.device)
+        else:
+            dst = out[i]
+            if dst.dtype != src.dtype or dst.device != src.device or tuple(dst.shape) != (B, tm, dim) or not dst.is_contiguous():
+                raise ValueError(f"collate: out[{i}] is not a contiguous {src.dtype} ({B}, {tm}, {dim}) tensor on the store's device")
+        tab[i] = _abi.CollateField(src.data_ptr(), s.row_start.data_ptr(), s.row_len.data_ptr(), dst.data_ptr(), eb, dim, tm)
+        outs.append(dst)
+    if utt is None:
+        utt = h2d([int(v) for v in idx], torch.int32, sources[0].src.device)
+    elif utt.dtype != torch.int32 or utt.numel() != B or not utt.is_contiguous() or utt.device != sources[0].src.device:
+        raise ValueError("collate: utt is ids as a contiguous int32 tensor on the stores' device")
+    _abi.check(lib.jatts_collate(tab, n_f, utt.data_ptr(), B, _stream()), "jatts_collate")
+    return outs
+
+
 # ---- training side (csrc/training.hip)
 def masked_loss(rb, a, b, valid_len, kind, scale, log_offset=-1.0):
     """scale * sum over valid rows of |a - b| (kind 0) or (a - b)^2 (kind 1); b -> log(b + log_offset) when log_offset >= 0."""

@@ -768,3 +768,342 @@ class VITSTrainer(FastSpeech2Trainer):
         return criterion(ret, batch["ilens"], batch["olens"], duration_loss=self.steps > self.dp_train_start_steps,
                          forward_sum=self.steps < self.dp_train_start_steps, bin_loss=self.steps > self.bin_loss_start_steps,
                          lambda_align=self.lambda_align, lambda_mel=self.lambda_mel)
+
+
+# ------------------------------------------------------------------------------------------ stage 3: config -> trainer, the loop
+# What the reference's tts_train.py reads from the recipe YAML (jatts/bin/tts_train.py:327-389) mapped onto the trainers above.  Whatever the
+# trainers cannot do is refused BY NAME here, at start-up; keys that nothing reads are logged by name (unread_keys).
+TRAINER_CLASSES = {"FastSpeech2Trainer": FastSpeech2Trainer, "MatchaTTSTrainer": MatchaTTSTrainer, "VITSTrainer": VITSTrainer}
+NO_EFFECT_KEYS = ("pin_memory", "num_workers", "allow_cache")      # DataLoader / dataset-cache knobs: the resident data path has neither
+# criterion name -> the only parameter values the trainers' criteria implement (the reference classes' defaults, jatts/losses/*.py)
+CRITERION_DEFAULTS = {
+    "MelLoss": {"_type": "L1Loss", "params": {}},
+    "DurationPredictorLoss": {"use_masking": True, "offset": 1.0, "reduction": "mean"},
+    "PitchLoss": {"use_masking": True, "reduction": "mean"},
+    "EnergyLoss": {"use_masking": True, "reduction": "mean"},
+    "EncoderPriorLoss": {"use_masking": True, "reduction": "mean"},
+    "CFMLoss": {},
+    "KLDivergenceLoss": {},
+    "ForwardSumLoss": {"cache_prior": True},
+}
+_TRAINER_CRITERIA = {
+    "FastSpeech2Trainer": ("MelLoss", "DurationPredictorLoss", "PitchLoss", "EnergyLoss"),
+    "MatchaTTSTrainer": ("CFMLoss", "EncoderPriorLoss", "ForwardSumLoss", "DurationPredictorLoss"),
+    "VITSTrainer": ("MelLoss", "KLDivergenceLoss", "ForwardSumLoss", "DurationPredictorLoss"),
+}
+_TRAINER_EXTRAS = {
+    "FastSpeech2Trainer": (),
+    "MatchaTTSTrainer": ("dp_train_start_steps", "bin_loss_start_steps", "lambda_align"),
+    "VITSTrainer": ("dp_train_start_steps", "bin_loss_start_steps", "lambda_align", "lambda_mel"),
+}
+
+
+_TRAINER_FEATURES = {"FastSpeech2Trainer": ("mel", "pitch", "energy"), "MatchaTTSTrainer": ("mel",), "VITSTrainer": ("mel", "spkemb")}
+# top-level keys of a recipe config that stage 3 reads (here, in tts_train and in run_training) ...
+READ_KEYS = ("feat_list", "out_feat_type", "model_type", "model_params", "trainer_type", "collater_type", "criterions", "vocoder", "batch_size",
+             "optimizer_type", "optimizer_params", "grad_norm", "scheduler_type", "scheduler_params", "gradient_accumulate_steps",
+             "dp_train_start_steps", "bin_loss_start_steps", "lambda_align", "lambda_mel", "freeze_modules", "train_max_steps", "save_interval_steps",
+             "eval_interval_steps", "log_interval_steps", "num_save_intermediate_results", "temperature", "ode_steps", "prompt_feat_list",
+             "prompt_strategy") + NO_EFFECT_KEYS
+# ... and those that belong to stage 1 (preprocess) or stage 4 (tts_decode) and mean nothing to training
+OTHER_STAGE_KEYS = ("sampling_rate", "fft_size", "hop_size", "win_length", "window", "num_mels", "fmin", "fmax", "global_gain_scale", "log_base",
+                    "pitch_extract_type", "pitch_extract_f0min", "pitch_extract_f0max", "energy_extract_type", "spkemb_checkpoint", "spkemb_params",
+                    "noise_scale")
+
+
+def unread_keys(config, cli_keys=()):
+    """Top-level config keys that stage 3 does not read and that are not another stage's: tts_train logs each by name (the FastSpeech2 and VITS
+    recipes' ``scheduler: warmuplr`` is one: the reference reads ``scheduler_type``, tts_train.py:349, and so does this package)."""
+    known = set(READ_KEYS) | set(OTHER_STAGE_KEYS) | set(cli_keys)
+    return [k for k in config if k not in known]
+
+
+def check_durations(config, has_durations):
+    """Ground-truth durations come from the csv's ``durations`` column: refused by name at start-up when the trainer needs them and the csv has none
+    (FastSpeech2Trainer always; MatchaTTSTrainer with the tts1 model ``MatchaTTS``; the MAS models find their own)."""
+    ttype, mtype = config.get("trainer_type"), config.get("model_type")
+    if not has_durations and (ttype == "FastSpeech2Trainer" or (ttype == "MatchaTTSTrainer" and mtype == "MatchaTTS")):
+        raise ValueError(f"durations: {ttype} with model_type {mtype} needs the csv's durations column, and the training csv has none")
+
+
+def trainer_kwargs(config):
+    """Recipe config (dict) -> (trainer class, keyword arguments).  Raises ValueError naming the option for: a ``trainer_type`` that is not
+    here, another ``optimizer_type`` than Adam, an ``optimizer_params`` key Adam-as-a-kernel does not take, another ``scheduler_type`` than
+    warmuplr / StepLR (the names tts_train.py:37-41 reads; exponentiallr is not here), a scheduler parameter the schedule does not have, a
+    criterion the trainer does not compute or a criterion parameter off its default, ``freeze_modules``, a ``feat_list`` without a feature the trainer's batch needs, and ``lambda_*`` / ``*_start_steps``
+    keys given to a trainer that has no such term."""
+    ttype = config.get("trainer_type", "ARTTSTrainer")
+    if ttype not in TRAINER_CLASSES:
+        raise ValueError(f"trainer_type: {ttype!r} is not on the HIP path ({', '.join(TRAINER_CLASSES)})")
+    otype = config.get("optimizer_type", "Adam")
+    if otype != "Adam":
+        raise ValueError(f"optimizer_type: {otype!r} is not implemented (the optimiser step is the Adam kernel jatts_adam_step)")
+    kw = {}
+    op = dict(config.get("optimizer_params") or {})
+    for k in op:
+        if k not in ("lr", "betas", "eps", "weight_decay"):
+            raise ValueError(f"optimizer_params: {k!r} is not implemented (lr, betas, eps, weight_decay)")
+    if "lr" in op:
+        kw["lr"] = float(op["lr"])
+    if "betas" in op:
+        kw["betas"] = tuple(float(b) for b in op["betas"])
+    if "eps" in op:
+        kw["eps"] = float(op["eps"])
+    if "weight_decay" in op:
+        kw["weight_decay"] = float(op["weight_decay"])
+    kw["grad_norm"] = float(config.get("grad_norm", 1.0))
+    stype = config.get("scheduler_type", "warmuplr")
+    sp = dict(config.get("scheduler_params") or {})
+    if stype == "warmuplr":
+        for k in sp:
+            if k != "warmup_steps":
+                raise ValueError(f"scheduler_params: {k!r} is not a parameter of warmuplr (warmup_steps)")
+        kw["scheduler"] = "warmuplr"
+        kw["warmup_steps"] = sp.get("warmup_steps", 25000)            # WarmupLR's own default (schedulers/warmup_lr.py)
+    elif stype == "StepLR":
+        for k in sp:
+            if k not in ("step_size", "gamma"):
+                raise ValueError(f"scheduler_params: {k!r} is not implemented for StepLR (step_size, gamma)")
+        if "step_size" not in sp:
+            raise ValueError("scheduler_params: StepLR needs step_size")
+        kw["scheduler"], kw["scheduler_params"] = "steplr", sp
+    else:
+        raise ValueError(f"scheduler_type: {stype!r} is not implemented (warmuplr, StepLR)")
+    kw["gradient_accumulate_steps"] = int(config.get("gradient_accumulate_steps", 1))
+    if config.get("freeze_modules"):
+        raise ValueError("freeze_modules: freezing modules is not implemented (every parameter lives in one flat optimiser buffer)")
+    for k in ("dp_train_start_steps", "bin_loss_start_steps", "lambda_align", "lambda_mel"):
+        if k in config:
+            if k not in _TRAINER_EXTRAS[ttype]:
+                raise ValueError(f"{k}: {ttype} has no such term")
+            kw[k] = config[k]
+    if "feat_list" in config:
+        for name in _TRAINER_FEATURES[ttype]:
+            if name not in config["feat_list"]:
+                raise ValueError(f"feat_list: {ttype} needs {name!r} (feat_list = {list(config['feat_list'])})")
+    for name, params in (config.get("criterions") or {}).items():
+        if name not in CRITERION_DEFAULTS or name not in _TRAINER_CRITERIA[ttype]:
+            raise ValueError(f"criterions: {name!r} is not computed by {ttype} ({', '.join(_TRAINER_CRITERIA[ttype])})")
+        for k, v in (params or {}).items():
+            if k not in CRITERION_DEFAULTS[name]:
+                raise ValueError(f"criterions: {name}.{k} is not a parameter of the criterion")
+            if v != CRITERION_DEFAULTS[name][k]:
+                raise ValueError(f"criterions: {name}.{k} = {v!r} is not implemented (only {CRITERION_DEFAULTS[name][k]!r})")
+    return TRAINER_CLASSES[ttype], kw
+
+
+# torch.nn.Embedding tables of the four model classes, by their full names (a suffix rule would also catch the pitch_embed / energy_embed convs)
+_EMBEDDING_TABLES = ("encoder.embed.0.weight", "text_encoder.emb.weight", "sid_emb.weight", "lid_emb.weight")
+
+
+@torch.no_grad()
+def initialize_parameters(model, init_type="xavier_uniform"):
+    """A model class of this package is built with every parameter zero (it is made to be loaded into).  Training from scratch needs what the
+    reference's constructors plus ``initialize(self, init_type)`` leave behind (jatts/modules/initialize.py:70-95, called from every model's
+    ``_reset_parameters``), restated on parameter names and shapes because the module tree here carries no layer types:
+      * parameters of two or more dimensions: ``init_type`` (xavier_uniform / xavier_normal / kaiming_uniform / kaiming_normal), pos_bias_u / v too;
+      * embedding tables (``Embedding.reset_parameters``): N(0, 1); the text embedding's padding row 0 (padding_idx = 0, fastspeech2.py:238,271) zero;
+      * ``*.bias``: zero;  one-dimensional ``*.weight`` (LayerNorm / GroupNorm / BatchNorm scales): one;
+      * other one-dimensional parameters (SnakeBeta's log-scale alpha / beta, matchatts/transformer.py:72-74): zero;
+      * BatchNorm ``running_var``: one, ``running_mean`` and ``num_batches_tracked``: zero.
+    The distributions are the reference's; the draws are not (its constructors consume torch's generator in another order)."""
+    fns = {"xavier_uniform": torch.nn.init.xavier_uniform_, "xavier_normal": torch.nn.init.xavier_normal_,
+           "kaiming_uniform": lambda t: torch.nn.init.kaiming_uniform_(t, nonlinearity="relu"),
+           "kaiming_normal": lambda t: torch.nn.init.kaiming_normal_(t, nonlinearity="relu")}
+    if init_type not in fns:
+        raise ValueError(f"init_type: {init_type!r} is not implemented ({', '.join(fns)})")
+    for name, p in model.named_parameters():
+        if p.dim() > 1:
+            if name in _EMBEDDING_TABLES and p.dim() == 2:
+                p.data.normal_(0.0, 1.0)
+                if name == "encoder.embed.0.weight":
+                    p.data[0].zero_()
+            else:
+                fns[init_type](p.data)
+        elif name.endswith(".weight"):
+            p.data.fill_(1.0)
+        else:
+            p.data.zero_()
+    for name, b in model.named_buffers():
+        if name.endswith("running_var"):
+            b.fill_(1.0)
+        elif name.endswith(("running_mean", "num_batches_tracked")):
+            b.zero_()
+    if hasattr(model, "_prep"):
+        model._prep = None
+    return model
+
+
+def broadcast_model(model, src=0, group=None):
+    """Every parameter and buffer of ``model`` as rank ``src`` holds it, in place on all ranks: what DistributedDataParallel does at construction for
+    the reference (tts_train.py:355-363).  The trainers all-reduce gradients only, so replicas that start apart stay apart: a from-scratch run draws
+    its initial parameters per rank (``initialize_parameters`` on each rank's own generator), and this call is what makes them one model.  No-op
+    without an initialised process group or at world size 1.  In place, so a trainer's flat views stay attached."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) < 2:
+        return model
+    with torch.no_grad():
+        for t in model.state_dict().values():
+            dist.broadcast(t, src, group=group)
+    if hasattr(model, "_prep"):
+        model._prep = None
+    return model
+
+
+def replica_spread(trainer, group=None):
+    """max - min over the ranks of the sum of all parameters (float64, fixed order): 0.0 while the replicas of a data-parallel job are one model
+    (same start, same averaged gradients, same clip + Adam).  A collective: every rank calls it.  0.0 without a process group."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) < 2:
+        return 0.0
+    s = trainer.flat_p.detach().double().sum().reshape(1)
+    lo, hi = s.clone(), s.clone()
+    dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group)
+    dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
+    return float(hi - lo)
+
+
+def _inference_kwargs(config):
+    if config.get("model_type") in ("MatchaTTS", "MatchaTTS_MAS"):          # trainers/matchatts.py: temperature / ode_steps of the config
+        return {"temperature": config.get("temperature", 0.667), "n_timesteps": config.get("ode_steps", 10)}
+    return {}
+
+
+@torch.no_grad()
+def save_intermediate_results(trainer, batch, config, outdir, vocoder=None):
+    """`_genearete_and_save_intermediate_result` (trainers/fastspeech2.py:102-223): up to ``num_save_intermediate_results`` utterances of a dev
+    batch through ``model.inference`` -> predictions/<steps>steps/{durations/<idx>.txt, wav/<idx>_gen.wav (with a vocoder), outs/<idx>_out.png
+    (where matplotlib imports)}."""
+    import logging
+    import os
+    dirname = os.path.join(outdir, "predictions", f"{trainer.steps}steps")
+    os.makedirs(os.path.join(dirname, "durations"), exist_ok=True)
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        plt = None
+        logging.info("matplotlib is not importable: figures are skipped.")
+    if vocoder is None:
+        logging.info("No vocoder: wav/<idx>_gen.wav is skipped (the reference's Griffin-Lim fallback is not part of this package).")
+    model, kw = trainer.model, _inference_kwargs(config)
+    was = model.training
+    model.eval()
+    try:
+        ilens, olens = batch["ilens"].tolist(), batch["olens"].tolist()
+        gt = batch["durations"].cpu() if batch.get("durations") is not None else None
+        for idx in range(min(len(ilens), int(config.get("num_save_intermediate_results", 4)))):
+            spk = None if batch.get("spkembs") is None else batch["spkembs"][idx]
+            ret = model.inference(batch["xs"][idx, :ilens[idx]], spembs=spk, **kw)
+            outs, d_outs = ret["feat_gen"], ret["duration"]
+            if plt is not None:
+                os.makedirs(os.path.join(dirname, "outs"), exist_ok=True)
+                plt.figure(figsize=(12, 4), dpi=150)
+                for i, a in enumerate((outs.float().cpu().numpy(), batch["ys"][idx, :olens[idx]].cpu().numpy()), 1):
+                    plt.subplot(1, 2, i)
+                    plt.imshow(a.T, aspect="auto", origin="lower")
+                plt.tight_layout()
+                plt.savefig(os.path.join(dirname, "outs", f"{idx}_out.png"))
+                plt.close()
+            if vocoder is not None:
+                from .bin.tts_decode import write_wav_pcm16
+                os.makedirs(os.path.join(dirname, "wav"), exist_ok=True)
+                y, sr = vocoder.decode(outs)
+                write_wav_pcm16(os.path.join(dirname, "wav", f"{idx}_gen.wav"), hip.pcm16(y.float().contiguous()).cpu().numpy(), sr)
+            d_out = [str(d) for d in d_outs.reshape(-1).cpu().numpy().tolist()]
+            with open(os.path.join(dirname, "durations", f"{idx}.txt"), "w") as f:
+                if gt is not None:
+                    for d_gt, d in zip(gt[idx, :ilens[idx]].numpy().tolist(), d_out):
+                        f.write(f"{d_gt} {d}\n")
+                else:
+                    f.write("".join(f"{d}\n" for d in d_out))
+    finally:
+        model.train(was)
+
+
+def run_training(trainer, train_loader, dev_loader, config, outdir, rank=0, vocoder=None, epochs=0):
+    """The reference's training loop (jatts/trainers/base.py:66-224) around ``trainer.train_step`` / ``eval_step``: epochs over
+    ``train_loader`` until ``trainer.steps`` reaches ``train_max_steps``; on rank 0, every ``log_interval_steps`` the mean of each loss since
+    the last log line as ``(Steps: N) train/<name> = x.xxxx.``, every ``eval_interval_steps`` the mean of ``eval_step`` over ``dev_loader`` as
+    ``eval/<name>`` plus the intermediate results of its first batch, every ``save_interval_steps`` ``checkpoint-<steps>steps.pkl``; and the
+    same checkpoint in a ``finally`` at exit (tts_train.py:402-408).  Losses are summed as device scalars and read back only when a line is
+    written: no host synchronisation in the steps between.  Every scalar also goes to ``<outdir>/scalars.jsonl`` and, where tensorboardX
+    imports, to a SummaryWriter.  -> {"steps", "epochs"}."""
+    import json
+    import logging
+    import os
+    os.makedirs(outdir, exist_ok=True)
+    max_steps = int(config["train_max_steps"])
+    every = {k: max(1, int(config[k + "_interval_steps"])) for k in ("log", "eval", "save")}
+    writer = None
+    if rank == 0:
+        try:
+            from tensorboardX import SummaryWriter
+            writer = SummaryWriter(outdir)
+        except ImportError:
+            logging.info("tensorboardX is not importable: scalars go to scalars.jsonl only.")
+
+    def write_scalars(prefix, sums, n):
+        vals = {f"{prefix}/{k}": v / n for k, v in sums.items()}
+        host = torch.stack([v.double().reshape(()) for v in vals.values()]).cpu().tolist() if vals else []      # ONE read-back per line block
+        with open(os.path.join(outdir, "scalars.jsonl"), "a") as f:
+            for k, v in zip(vals, host):
+                logging.info(f"(Steps: {trainer.steps}) {k} = {v:.4f}.")
+                f.write(json.dumps({"steps": trainer.steps, "tag": k, "value": v}) + "\n")
+                if writer is not None:
+                    writer.add_scalar(k, v, trainer.steps)
+
+    def add(sums, losses):
+        for k, v in losses.items():
+            v = v.detach().double()
+            sums[k] = v if k not in sums else sums[k] + v
+
+    def evaluate():
+        logging.info(f"(Steps: {trainer.steps}) Start evaluation.")
+        sums, n = {}, 0
+        for n, batch in enumerate(dev_loader, 1):
+            add(sums, trainer.eval_step(batch))
+            if n == 1:
+                save_intermediate_results(trainer, batch, config, outdir, vocoder)
+        logging.info(f"(Steps: {trainer.steps}) Finished evaluation ({n} steps per epoch).")
+        if n:
+            write_scalars("eval", sums, n)
+
+    def save():
+        trainer.save_checkpoint(os.path.join(outdir, f"checkpoint-{trainer.steps}steps.pkl"), epochs=epochs)
+        logging.info(f"Successfully saved checkpoint @ {trainer.steps} steps.")
+
+    sums, n_sum = {}, 0
+    finished = trainer.steps >= max_steps
+    train_loader.set_epoch(epochs)
+    try:
+        while not finished:
+            per_epoch = 0
+            for per_epoch, batch in enumerate(train_loader, 1):
+                add(sums, trainer.train_step(batch))
+                n_sum += 1
+                if trainer._micro != 0:              # gradient accumulation: the optimiser has not stepped yet (base.py:135-136)
+                    continue
+                finished = trainer.steps >= max_steps
+                if rank == 0:
+                    if trainer.steps % every["log"] == 0:
+                        write_scalars("train", sums, n_sum)
+                        sums, n_sum = {}, 0
+                    if trainer.steps % every["eval"] == 0:
+                        evaluate()
+                    if trainer.steps % every["save"] == 0:
+                        save()
+                if finished:
+                    break
+            else:
+                epochs += 1
+                logging.info(f"(Steps: {trainer.steps}) Finished {epochs} epoch training ({per_epoch} steps per epoch).")
+                train_loader.set_epoch(epochs)       # needed for the shuffle in distributed training (base.py:156-158)
+                if per_epoch == 0:
+                    raise ValueError("the training loader yields no batch")
+        logging.info("Finished training.")
+    finally:
+        if rank == 0:
+            save()
+            if writer is not None:
+                writer.close()
+    return {"steps": trainer.steps, "epochs": epochs}
