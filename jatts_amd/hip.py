@@ -225,13 +225,13 @@ def _dev(t):
     return t
 
 
-_KEEP = [None]        # while a training step is being captured: every cached device tensor handed out (the graph bakes their addresses in)
+_KEEP = [None]        # while a graph is being captured (graphs.capture): every cached device tensor handed out (the graph bakes their addresses in)
 
 
 def keep_begin():
     """Start recording the cached device tensors handed out from here on (hip.h2d, RaggedBatch geometry, the models' per-length tables):
     a captured graph reads them at their addresses for as long as it is replayed, while the caches are bounded and evict -- the capture's
-    owner keeps the returned list alive next to the graph (jatts_amd.training)."""
+    owner keeps the returned list alive next to the graph (jatts_amd.graphs.capture, the only caller)."""
     _KEEP[0] = []
     return _KEEP[0]
 
@@ -1846,6 +1846,12 @@ def masked_loss_bwd(rb, a, b, valid_len, kind, scale, upstream=None, log_offset=
                                          float(log_offset), float(scale), _ptr(upstream), da.data_ptr(), a2.shape[1], _stream()),
                "jatts_masked_loss_bwd")
     return da.view_as(a)
+
+
+def dropout_base_seed(seed, rank):
+    """Base of one forward pass's dropout masks (site n draws from base + n): `seed` is the trainer's step / micro-batch counter, and
+    data-parallel replicas draw different masks.  The eager forward bakes it into its launches, a replayed graph reads it from seed_dev."""
+    return (int(seed) * 4099 + int(rank)) * 1000003
 
 
 def dropout(x, p, seed, seed_dev=None):

@@ -27,7 +27,7 @@ class _Ctx:
         rank = 0
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             rank = torch.distributed.get_rank()          # data-parallel replicas draw different dropout masks
-        self.seed = (int(seed) * 4099 + rank) * 1000003
+        self.seed = hip.dropout_base_seed(seed, rank)
         # graph mode (training.py): the per-step base seed lives in a device tensor the trainer rewrites before every replay; the call
         # sites then pass only their offset
         self.seed_dev = getattr(model, "_seed_dev", None)

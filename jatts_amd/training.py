@@ -16,17 +16,13 @@ import contextlib
 import torch
 import torch.distributed as dist
 
-from . import hip
+from . import graphs, hip
 from .models._conformer import PackedConv
 
 L1, L2 = 0, 1
 
 
 # ------------------------------------------------------------------------------------------ criterion
-def _padded(rb_len, B):
-    return hip.RaggedBatch([rb_len] * B, torch.device("cuda", torch.cuda.current_device()))
-
-
 @torch.no_grad()
 def fastspeech2_losses(ret, durations, pitch, energy, ilens, use_masking=True):
     """`_train_step`'s loss block (trainers/fastspeech2.py:62-84) on FastSpeech2.forward()'s return dict.
@@ -61,12 +57,16 @@ SPLIT_CONVS = [False]
 
 
 @contextlib.contextmanager
-def split_convs(on=True):
-    prev, SPLIT_CONVS[0] = SPLIT_CONVS[0], bool(on)
+def _switched(flag, on):
+    prev, flag[0] = flag[0], bool(on)
     try:
         yield
     finally:
-        SPLIT_CONVS[0] = prev
+        flag[0] = prev
+
+
+def split_convs(on=True):
+    return _switched(SPLIT_CONVS, on)
 
 
 # precision="fp32_bf16x3" of the trainers (round 7): the same convs on the f32-EQUIVALENT emulated arithmetic (JATTS_F32E: three exact bf16 terms per
@@ -84,13 +84,8 @@ TRAIN_PRECISIONS = {
 }
 
 
-@contextlib.contextmanager
 def emul_convs(on=True):
-    prev, EMUL_CONVS[0] = EMUL_CONVS[0], bool(on)
-    try:
-        yield
-    finally:
-        EMUL_CONVS[0] = prev
+    return _switched(EMUL_CONVS, on)
 
 
 # attention="fp32_bf16x3" of the trainers (round 10): the attention products of autograd.BMM -- q k^T, q p^T, P v, the Gaussian-upsampling p_up @ hs (while autograd.MAS_OWN_KERNELS leaves it on BMM) and their
@@ -102,13 +97,8 @@ TRAIN_ATTENTIONS = {
 }
 
 
-@contextlib.contextmanager
 def emul_attention(on=True):
-    prev, EMUL_ATTENTION[0] = EMUL_ATTENTION[0], bool(on)
-    try:
-        yield
-    finally:
-        EMUL_ATTENTION[0] = prev
+    return _switched(EMUL_ATTENTION, on)
 
 
 def emul_bgemm_wins(m, n, k):
@@ -271,6 +261,38 @@ def scheduled_lr(kind, base_lr, step_num, **params):
     raise ValueError(f"unknown scheduler {kind!r} (warmuplr, steplr, none)")
 
 
+class _ScalarRing:
+    """A replayed graph's per-step scalars (dropout seed and Adam scalars in, gradient norm out) travel through a RING of pinned staging buffers, each
+    guarded by an event recorded behind its copies: the host may run many steps ahead of the GPU, and one shared set would let step N's copy read step N + 1's."""
+
+    def __init__(self, n):
+        self.slots = [dict(seed=torch.zeros(1, dtype=torch.int64).pin_memory(), hyper=torch.zeros(7, dtype=torch.float32).pin_memory(),
+                           gn=torch.zeros(1, dtype=torch.float64).pin_memory(), step=0, ev=None) for _ in range(n)]
+        self.pos = 0
+
+    def check(self, sanity):
+        """Read the gradient norm of every finished slot and of the slot about to be recycled (waited for), so that no step's norm goes unread."""
+        nxt = self.slots[self.pos % len(self.slots)]
+        for sl in self.slots:
+            if sl["ev"] is None or not sl["step"] or not (sl is nxt or sl["ev"].query()):
+                continue                     # (never used, already read, or still in flight)
+            if sl is nxt:
+                sl["ev"].synchronize()       # (normally done long since)
+            v = float(sl["gn"][0])
+            sl["step"] = 0
+            if not (v == v and abs(v) < sanity):
+                raise FloatingPointError(f"gradient norm {v} at trainer step {sl['at']} (graph replay): a diverged run or a capture that does not replay correctly -- "
+                                         "replay of this batch signature is disabled, later steps of it run eagerly; the parameters are suspect: resume from the last checkpoint")
+
+    def take(self):
+        """-> the next slot, its copies of len(slots) steps ago done; the caller fills it, replays, and records slot["ev"] behind its copies."""
+        slot = self.slots[self.pos % len(self.slots)]
+        self.pos += 1
+        if slot["ev"] is not None:
+            slot["ev"].synchronize()         # (already waited for by check() when it held a step's norm)
+        return slot
+
+
 class FastSpeech2Trainer:
     """`FastSpeech2Trainer._train_step` (jatts/trainers/fastspeech2.py:24-100) on one GPU of a data-parallel job:
     forward (train mode) -> MelLoss + DurationPredictorLoss + PitchLoss + EnergyLoss -> backward -> gradient all-reduce over
@@ -322,11 +344,11 @@ class FastSpeech2Trainer:
         self.last_lr = None
         self._bad_ids = None
         # graph mode: the whole step (forward, losses, backward, clip + Adam) of a batch SIGNATURE (shapes + length tuples: a length bucket)
-        # captured once as a hipGraph and replayed; the first step of a signature runs eagerly (it fills every per-lengths cache), the
-        # second is captured.  See _graph_step.
-        self.capture_graph = bool(capture_graph) and self._graph_capable
-        self._graphs = {}
-        self.max_graphs = max(1, int(max_graphs))     # captured graphs kept (each owns the activations of one step: GBs); least recently used evicted
+        # captured once as a hipGraph and replayed, under the rules of jatts_amd/graphs.py.  See _graph_step.
+        self.capture_graph = bool(capture_graph)
+        self.max_graphs = max(1, int(max_graphs))     # captured graphs kept (each owns the activations of one step: GBs)
+        self._policy = graphs.GraphPolicy()
+        self._graphs = self._policy.states            # signature -> state dict
         self._buckets = None
 
     # -- gradients into the flat buffer.  With .grad pre-set to views of flat_g, autograd's AccumulateGrad runs one `view += g` kernel per
@@ -481,22 +503,23 @@ class FastSpeech2Trainer:
                             sids=batch.get("sids"), seed=self._seed())
         return criterion(ret, batch["durations"], batch["pitch"], batch["energys"], batch["ilens"])
 
+    def _loss_phase(self):      # read ONCE per train_step / eval_step, before `steps` moves: what keys the graph is what compute_losses builds
+        return None             # (no schedule here: _ScheduledTrainer)
+
     @torch.no_grad()
     def eval_step(self, batch):
-        with precision_convs(self.precision), emul_attention(self.attention == "fp32_bf16x3"):
-            return self._eval_step(batch)
-
-    def _eval_step(self, batch):
         """`_eval_step` of the reference trainers (e.g. trainers/fastspeech2.py:150-215): the same forward + criterion in eval() mode
         (running-statistics BatchNorm, no dropout), no gradients, no update.  -> dict of loss tensors."""
+        self._phase = self._loss_phase()
         was = self.model.training
         self.model.eval()
         try:
-            return {k: v.detach() for k, v in self.compute_losses(batch).items()}
+            with precision_convs(self.precision), emul_attention(self.attention == "fp32_bf16x3"):
+                return {k: v.detach() for k, v in self.compute_losses(batch).items()}
         finally:
             self.model.train(was)
 
-    _graph_capable = True      # a subclass whose step synchronises with the host switches it off
+    _phase = None              # _loss_phase() of the running call
     SCALAR_RING = 8            # pinned staging slots for the per-step scalars of a replayed graph
     GRAD_NORM_SANITY = 1e12    # a replayed step whose (pre-clip) gradient norm is not finite or beyond this is treated as a broken capture
 
@@ -514,111 +537,64 @@ class FastSpeech2Trainer:
                 sig.append((k, repr(v)))
         return tuple(sig)
 
-    def _graph_step(self, batch):
-        """One optimiser step by graph replay.  Preconditions (checked where they can be): world size 1, no gradient accumulation, the
-        length vectors (ilens / olens / *_lens) are CPU tensors, sum(durations) == olens per utterance."""
-        dev = self.flat_p.device
-        sig = self._signature(batch)
-        st = self._graphs.get(sig)
-        if st is not None and st.get("eager_only"):
-            return self._train_step(batch)
-        if st is None:                       # first sight of this bucket: eager step, remember the verified frame counts
-            if "durations" in batch and batch["durations"] is not None:
-                dsum = [int(v) for v in batch["durations"].sum(1).tolist()]
-                if dsum != [int(v) for v in batch["olens"].tolist()]:
-                    raise ValueError("graph mode needs sum(durations) == olens for every utterance")
-            if len(self._graphs) >= 16 * max(1, self.max_graphs):      # signatures seen once and never again (unbucketed data): bounded
-                for k in [k for k, v in self._graphs.items() if v.get("graph") is None and not v.get("eager_only")][: len(self._graphs) // 2]:   # (eager-only markers stay)
-                    del self._graphs[k]
-            self._graphs[sig] = {"graph": None}
-            return self._train_step(batch)
-        if st["graph"] is None:              # second sight: capture
-            live = [(v.get("used", 0), k) for k, v in self._graphs.items() if v.get("graph") is not None]
-            while len(live) >= self.max_graphs:               # a bucketed sampler can produce many signatures: bound the graphs' memory
-                live.sort()
-                _, k = live.pop(0)
-                self._graphs[k] = {"graph": None}             # (its next sight captures again)
-            st["in"] = {k: (v.to(dev).clone() if torch.is_tensor(v) and (v.is_cuda or v.dim() != 1 or v.dtype not in (torch.int64, torch.int32)) else v)
-                        for k, v in batch.items()}
-            st["seed"] = torch.zeros(1, dtype=torch.int64, device=dev)
-            st["hyper"] = torch.zeros(7, dtype=torch.float32, device=dev)
-            # per-step scalars travel through a RING of pinned staging buffers, each guarded by an event recorded behind its copies: the
-            # host may run many steps ahead of the GPU (losses stay on the device), and one shared staging pair would let step N's
-            # asynchronous copy read step N + 1's values
-            st["ring"] = [dict(seed=torch.zeros(1, dtype=torch.int64).pin_memory(), hyper=torch.zeros(7, dtype=torch.float32).pin_memory(),
-                               gn=torch.zeros(1, dtype=torch.float64).pin_memory(), step=0, ev=None) for _ in range(self.SCALAR_RING)]
-            st["ring_pos"] = 0
-            m = self.model
-            m._seed_dev, m._static_olens = st["seed"], [int(v) for v in batch["olens"].tolist()]
-            g = torch.cuda.CUDAGraph()
-            # every cached device tensor the step is handed during the capture (length uploads, ragged geometry, positional tables, the
-            # forward-sum prior, frame / token selectors) lives in bounded caches that evict: the graph reads them at their addresses on
-            # every replay, so the graph's own record pins them
-            st["keep"] = hip.keep_begin()
-            try:
-                torch.cuda.synchronize()
-                with torch.cuda.graph(g):
-                    hip.zero_pool_begin(dev)
-                    self.flat_g.zero_()
-                    self._detach_grads()
-                    losses = self.compute_losses(st["in"])
-                    losses["loss"].backward()
-                    self._gather_grads(False)
-                    ss = None
-                    if self.grad_norm and self.grad_norm > 0:
-                        ss = torch.zeros((), dtype=torch.float64, device=dev)
-                        hip.sumsq(self.flat_g, ss)
-                    hip.adam_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, 0.0, self.betas[0], self.betas[1], self.eps, self.wd, 1,
-                                  grad_sumsq=ss, max_norm=self.grad_norm or 0.0, hyper_dev=st["hyper"])
-                    st["out"] = {k: v.detach() for k, v in losses.items()}
-                    if ss is not None:
-                        st["out"]["grad_norm"] = ss.sqrt()
-            except BaseException:
-                # a failed capture must not be retried forever, nor leave the parameters without their .grad views: this signature runs eagerly
-                self._graphs[sig] = {"graph": None, "eager_only": True}
-                for p_, v_ in zip(self.params, self._grad_views):
-                    p_.grad = v_
-                raise
-            finally:
-                hip.keep_end()
-                hip.zero_pool_end()
-                m._seed_dev, m._static_olens = None, None
-            st["graph"] = g
-        # replay: refresh the static inputs and the per-step scalars (all stream-ordered copies; no host wait)
+    def _optimiser_tail(self, lr, step, hyper_dev=None):
+        """clip_grad_norm_ + Adam on the flat buffers, on the host's (lr, step) or, inside a capture, on `hyper_dev` (hip.adam_hyper, rewritten
+        before every replay).  -> the float64 sum of squares of the gradient, or None without clipping."""
+        ss = None
+        if self.grad_norm and self.grad_norm > 0:
+            ss = torch.zeros((), dtype=torch.float64, device=self.flat_g.device)
+            hip.sumsq(self.flat_g, ss)
+        hip.adam_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, lr, self.betas[0], self.betas[1], self.eps, self.wd, step,
+                      grad_sumsq=ss, max_norm=self.grad_norm or 0.0, hyper_dev=hyper_dev)
+        return ss
+
+    def _capture_step(self, batch, sig, st):
+        """The whole step on static inputs, recorded into st["graph"] (graphs.capture): seed and Adam scalars read from device tensors."""
+        dev, m = self.flat_p.device, self.model
+        st["in"] = {k: (v.to(dev).clone() if torch.is_tensor(v) and (v.is_cuda or v.dim() != 1 or v.dtype not in (torch.int64, torch.int32)) else v)
+                    for k, v in batch.items()}
+        st["seed"], st["hyper"] = torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(7, dtype=torch.float32, device=dev)
+        st["ring"] = _ScalarRing(self.SCALAR_RING)
+        m._seed_dev, m._static_olens = st["seed"], [int(v) for v in batch["olens"].tolist()]
+        try:
+            with graphs.capture(self._policy, sig, st):
+                hip.zero_pool_begin(dev)
+                self.flat_g.zero_()
+                self._detach_grads()
+                losses = self.compute_losses(st["in"])
+                losses["loss"].backward()
+                self._gather_grads(False)
+                ss = self._optimiser_tail(0.0, 1, st["hyper"])
+                st["out"] = {k: v.detach() for k, v in losses.items()}
+                if ss is not None:
+                    st["out"]["grad_norm"] = ss.sqrt()
+        finally:
+            hip.zero_pool_end()
+            m._seed_dev, m._static_olens = None, None
+            for p_, v_ in zip(self.params, self._grad_views):      # (a failed capture must not leave the parameters without their .grad views)
+                p_.grad = v_
+
+    def _graph_step(self, batch, sig, st):
+        """One optimiser step by replay of st["graph"] on refreshed static inputs and per-step scalars (all stream-ordered copies; no host wait).  Preconditions
+        (checked where they can be): world size 1, no gradient accumulation, the length vectors (ilens / olens / *_lens) are CPU tensors, sum(durations) == olens."""
         if self._bad_ids is not None and self._bad_ids():       # out-of-range token ids of an EARLIER replay (zero rows, counted on the
             self._bad_ids = None                                # device by the embedding kernel inside the graph): IndexError, one step late
-        # guard (ADVICE r3 / r4): the gradient norm of every replayed step comes back through the ring.  A finished slot that holds a non-finite
-        # or absurd norm means either a replay that produced garbage (a reduction that does not survive capture on this stack, see _graph_step's
-        # notes) or a genuinely diverged run; either way: refuse to go on silently -- the signature is marked eager-only and the call raises, a
-        # few steps late, without a host sync per step, BEFORE this call has advanced the step counter / learning-rate schedule or touched
-        # the static inputs.  A slot about to be recycled is waited for and checked too, so no step's norm goes unread.
-        nxt = st["ring"][st["ring_pos"] % len(st["ring"])]
-        for sl in st["ring"]:
-            if sl["ev"] is None or not sl["step"]:
-                continue
-            if sl is nxt:
-                sl["ev"].synchronize()       # this slot's copies of SCALAR_RING steps ago have run (normally long since)
-            elif not sl["ev"].query():
-                continue
-            v = float(sl["gn"][0])
-            sl["step"] = 0
-            if not (v == v and abs(v) < self.GRAD_NORM_SANITY):
-                self._graphs[sig] = {"graph": None, "eager_only": True}
-                raise FloatingPointError(f"gradient norm {v} at trainer step {sl['at']} (graph replay): a diverged run or a capture that does not replay "
-                                         "correctly -- replay of this batch signature is disabled, later steps of it run eagerly; the parameters are "
-                                         "suspect: resume from the last checkpoint")
+        # guard (ADVICE r3 / r4): a replay that produced garbage or a genuinely diverged run; either way the signature is marked eager-only and the
+        # call raises, a few steps late, no host sync per step, BEFORE it has advanced the step counter / lr schedule or touched the static inputs
+        try:
+            st["ring"].check(self.GRAD_NORM_SANITY)
+        except FloatingPointError:
+            self._policy.fail(sig)
+            raise
         for k, v in batch.items():
             if torch.is_tensor(v) and torch.is_tensor(st["in"].get(k)) and st["in"][k].is_cuda:
                 st["in"][k].copy_(v, non_blocking=True)
+        seed = self._seed()                  # (the step's dropout stream: the one an eager step would draw from)
         self.steps += 1
-        lr = scheduled_lr(self.scheduler, self.base_lr, self.steps, **self._sched_params())
-        self.last_lr = lr
+        lr = self.last_lr = scheduled_lr(self.scheduler, self.base_lr, self.steps, **self._sched_params())
         rank = dist.get_rank(self.group) if dist.is_available() and dist.is_initialized() else 0
-        slot = st["ring"][st["ring_pos"] % len(st["ring"])]
-        st["ring_pos"] += 1
-        if slot["ev"] is not None:
-            slot["ev"].synchronize()         # (already waited for by the guard when it held a step's norm)
-        slot["seed"][0] = ((self.steps - 1) * self.accumulate + 1) * 4099 * 1000003 + rank * 1000003   # == _Ctx's (seed * 4099 + rank) * 1000003
+        slot = st["ring"].take()
+        slot["seed"][0] = hip.dropout_base_seed(seed, rank)
         slot["hyper"].copy_(torch.tensor(hip.adam_hyper(lr, self.betas[0], self.betas[1], self.eps, self.wd, self.steps), dtype=torch.float32))
         st["seed"].copy_(slot["seed"], non_blocking=True)
         st["hyper"].copy_(slot["hyper"], non_blocking=True)
@@ -628,49 +604,42 @@ class FastSpeech2Trainer:
             slot["step"], slot["at"] = 1, self.steps
         slot["ev"] = torch.cuda.Event()
         slot["ev"].record()
-        st["used"] = self.steps
         self.model._prep = None
         if self._bad_ids is None:
-            self._bad_ids = hip.bad_ids_async(dev)
+            self._bad_ids = hip.bad_ids_async(self.flat_p.device)
         # the graph's outputs are STATIC tensors that the next replay overwrites: hand out stream-ordered copies (one concatenation per dtype),
         # so that a caller who collects loss tensors and reads them later sees each step's own values
         out, by_dtype = {}, {}
         for k, v in st["out"].items():
             by_dtype.setdefault(v.dtype, []).append(k)
         for ks in by_dtype.values():
-            vals = torch.stack([st["out"][k].reshape(()) for k in ks])
-            for i, k in enumerate(ks):
-                out[k] = vals[i]
+            out.update(zip(ks, torch.stack([st["out"][k].reshape(()) for k in ks]).unbind(0)))
         return out
 
     def train_step(self, batch):
-        # (around the whole step: compute_losses and the backward of _train_step and of _graph_step's eager, capturing and replaying forms)
-        with precision_convs(self.precision), emul_attention(self.attention == "fp32_bf16x3"):
-            return self._train_step_any(batch)
-
-    def _train_step_any(self, batch):
         """batch: dict with the collater's keys (xs, ilens, ys, olens, durations, duration_lens, pitch, pitch_lens, energys,
         energy_lens).  -> dict of the loss tensors (on the GPU; .item() them only when logging)."""
-        m = self.model
-        m.train()
+        self.model.train()
+        self._phase = self._loss_phase()
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
-        if self.capture_graph and not multi and self.accumulate == 1:
-            sig_seen = self._graphs.get(self._signature(batch))
-            if sig_seen is not None and not sig_seen.get("eager_only"):
-                return self._graph_step(batch)          # capture / replay
-            hip.zero_pool_begin(self.flat_p.device)
+        with precision_convs(self.precision), emul_attention(self.attention == "fp32_bf16x3"):      # around the eager, capturing and replaying forms
+            if self.capture_graph and not multi and self.accumulate == 1:
+                sig = self._signature(batch)
+                if sig not in self._graphs and batch.get("durations") is not None:      # first sight of this bucket: verify the frame counts
+                    if [int(v) for v in batch["durations"].sum(1).tolist()] != [int(v) for v in batch["olens"].tolist()]:
+                        raise ValueError("graph mode needs sum(durations) == olens for every utterance")
+                act, st = self._policy.decide(sig, self.max_graphs, 16 * max(1, self.max_graphs))      # (once-seen signatures: unbucketed data)
+                if act == "capture":
+                    self._capture_step(batch, sig, st)
+                if act != "eager":                          # (no zero pool around it: the graph opens its own)
+                    return self._graph_step(batch, sig, st)
+            hip.zero_pool_begin(self.flat_p.device)     # the step's small zero-initialised accumulators: one fill instead of ~550
             try:
-                return self._graph_step(batch)          # first sight: eager (inside an open zero pool, like every eager step)
+                return self._train_step(batch)
             finally:
                 hip.zero_pool_end()
-        hip.zero_pool_begin(self.flat_p.device)     # the step's small zero-initialised accumulators: one fill instead of ~550
-        try:
-            return self._train_step(batch)
-        finally:
-            hip.zero_pool_end()
 
     def _train_step(self, batch):
-        m = self.model
         if self._bad_ids is not None and self._bad_ids():       # out-of-range token ids of an EARLIER step (zero rows, counted on the
             self._bad_ids = None                                # device): raised here, one step late, instead of a host sync per step
         if self._micro == 0:
@@ -699,15 +668,9 @@ class FastSpeech2Trainer:
         elif multi:
             allreduce_flat(self.flat_g, self.group, self.bucket_bytes)
         self.steps += 1
-        lr = scheduled_lr(self.scheduler, self.base_lr, self.steps, **self._sched_params())
-        self.last_lr = lr
-        ss = None
-        if self.grad_norm and self.grad_norm > 0:
-            ss = torch.zeros((), dtype=torch.float64, device=self.flat_g.device)
-            hip.sumsq(self.flat_g, ss)
-        hip.adam_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, lr, self.betas[0], self.betas[1], self.eps, self.wd, self.steps,
-                      grad_sumsq=ss, max_norm=self.grad_norm or 0.0)
-        m._prep = None
+        lr = self.last_lr = scheduled_lr(self.scheduler, self.base_lr, self.steps, **self._sched_params())
+        ss = self._optimiser_tail(lr, self.steps)
+        self.model._prep = None
         if self._bad_ids is None:
             self._bad_ids = hip.bad_ids_async(self.flat_p.device)
         losses = {k: v.detach() for k, v in losses.items()}
@@ -716,58 +679,61 @@ class FastSpeech2Trainer:
         return losses
 
 
-class MatchaTTSTrainer(FastSpeech2Trainer):
+def loss_phase(steps, dp_train_start_steps, bin_loss_start_steps):
+    """The scheduled loss terms of the step that follows `steps` optimiser steps (trainers/matchatts.py:66-103, vits.py:75-110), as the
+    criteria's keyword arguments: duration loss after dp_train_start_steps, forward-sum loss before it, binarisation loss after its own start."""
+    return dict(duration_loss=steps > dp_train_start_steps, forward_sum=steps < dp_train_start_steps, bin_loss=steps > bin_loss_start_steps)
+
+
+class _ScheduledTrainer(FastSpeech2Trainer):
+    """The loss schedule of the Matcha-TTS and VITS trainers: loss_phase() of the call, part of the graph's signature."""
+
+    def __init__(self, model, dp_train_start_steps=0, bin_loss_start_steps=0, lambda_align=2.0, **kw):
+        super().__init__(model, **kw)
+        self.dp_train_start_steps, self.bin_loss_start_steps, self.lambda_align = dp_train_start_steps, bin_loss_start_steps, lambda_align
+        self._phase = self._loss_phase()      # (train_step / eval_step refresh it: a direct compute_losses() sees the phase of the last call)
+
+    def _loss_phase(self):
+        return loss_phase(self.steps, self.dp_train_start_steps, self.bin_loss_start_steps)
+
+    def _signature(self, batch):
+        return super()._signature(batch) + (("schedule", *self._phase.values()),)
+
+
+class MatchaTTSTrainer(_ScheduledTrainer):
     """`MatchaTTSTrainer._train_step` (jatts/trainers/matchatts.py:23-120) for the tts1 recipe (ground-truth durations; criterions
     CFMLoss + EncoderPriorLoss + DurationPredictorLoss, conf/matcha_tts.v1.prior.steplr.large.yaml): same flat-buffer optimiser,
     all-reduce and checkpoint layout as FastSpeech2Trainer; the duration loss joins once `steps > dp_train_start_steps`
     (trainers/matchatts.py:66-75).  ``cfm_t`` / ``cfm_noise`` in the batch inject the two random draws of CFM.compute_loss."""
 
     # graph mode: the CFM draws are device draws (graph-safe through torch's generator); the MAS model's search, its durations and the
-    # Gaussian upsampling they drive all stay on the device, so its step captures too.  The loss schedule is part of the signature.
-
-    def __init__(self, model, dp_train_start_steps=0, bin_loss_start_steps=0, lambda_align=2.0, **kw):
-        super().__init__(model, **kw)
-        self.dp_train_start_steps, self.bin_loss_start_steps, self.lambda_align = dp_train_start_steps, bin_loss_start_steps, lambda_align
-
-    def _signature(self, batch):      # the loss schedule is part of the graph
-        return super()._signature(batch) + (("schedule", self.steps > self.dp_train_start_steps, self.steps < self.dp_train_start_steps,
-                                             self.steps > self.bin_loss_start_steps),)
-
+    # Gaussian upsampling they drive all stay on the device, so its step captures too.
     def compute_losses(self, batch):
         from .models.matchatts_train import criterion, train_forward
-        m = self.model
+        m, ph = self.model, self._phase
         mas = m._MAS      # tts2 MatchaTTS_MAS: alignment module + MAS; + ForwardSumLoss / binarisation loss by schedule
         ret = train_forward(m, batch["xs"], batch["ilens"], batch["ys"], batch["olens"], batch.get("durations"), batch.get("duration_lens"),
                             spembs=batch.get("spkembs"), sids=batch.get("sids"), cfm_t=batch.get("cfm_t"), cfm_noise=batch.get("cfm_noise"),
                             seed=self._seed())
-        return criterion(ret, batch.get("durations"), batch["ilens"], duration_loss=self.steps > self.dp_train_start_steps,
-                         olens=batch["olens"], forward_sum=mas and self.steps < self.dp_train_start_steps,
-                         bin_loss=mas and self.steps > self.bin_loss_start_steps, lambda_align=self.lambda_align)
+        return criterion(ret, batch.get("durations"), batch["ilens"], duration_loss=ph["duration_loss"], olens=batch["olens"],
+                         forward_sum=mas and ph["forward_sum"], bin_loss=mas and ph["bin_loss"], lambda_align=self.lambda_align)
 
 
-class VITSTrainer(FastSpeech2Trainer):
+class VITSTrainer(_ScheduledTrainer):
     """`VITSTrainer._train_step` (jatts/trainers/vits.py:23-140) for the mel-VITS: lambda_mel x MelLoss + KLDivergenceLoss, the
     duration loss after `dp_train_start_steps`, lambda_align x ForwardSumLoss before it, lambda_align x the binarisation loss
     after `bin_loss_start_steps`; same flat-buffer optimiser / all-reduce / checkpoint layout.  ``post_noise`` in the batch
     injects the posterior encoder's random draw.  (gradient_accumulate_steps = 1.)"""
 
     def __init__(self, model, dp_train_start_steps=0, bin_loss_start_steps=0, lambda_align=2.0, lambda_mel=1.0, **kw):
-        super().__init__(model, **kw)
-        self.dp_train_start_steps, self.bin_loss_start_steps = dp_train_start_steps, bin_loss_start_steps
-        self.lambda_align, self.lambda_mel = lambda_align, lambda_mel
-
-    def _signature(self, batch):      # the loss schedule is part of the graph
-        return super()._signature(batch) + (("schedule", self.steps > self.dp_train_start_steps, self.steps < self.dp_train_start_steps,
-                                             self.steps > self.bin_loss_start_steps),)
+        super().__init__(model, dp_train_start_steps, bin_loss_start_steps, lambda_align, **kw)
+        self.lambda_mel = lambda_mel
 
     def compute_losses(self, batch):
         from .models.vits_train import criterion, train_forward
-        m = self.model
-        ret = train_forward(m, batch["xs"], batch["ilens"], batch["ys"], batch["olens"], batch["spkembs"], post_noise=batch.get("post_noise"),
-                            seed=self._seed())
-        return criterion(ret, batch["ilens"], batch["olens"], duration_loss=self.steps > self.dp_train_start_steps,
-                         forward_sum=self.steps < self.dp_train_start_steps, bin_loss=self.steps > self.bin_loss_start_steps,
-                         lambda_align=self.lambda_align, lambda_mel=self.lambda_mel)
+        ret = train_forward(self.model, batch["xs"], batch["ilens"], batch["ys"], batch["olens"], batch["spkembs"],
+                            post_noise=batch.get("post_noise"), seed=self._seed())
+        return criterion(ret, batch["ilens"], batch["olens"], **self._phase, lambda_align=self.lambda_align, lambda_mel=self.lambda_mel)
 
 
 # ------------------------------------------------------------------------------------------ stage 3: config -> trainer, the loop

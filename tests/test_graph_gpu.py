@@ -120,6 +120,27 @@ def test_graph_cache_evicts_least_recently_used(cuda, lib):
     assert len(gc) == 2 and gc.stats["captured"] == 4      # "a" was evicted by "c" and captured again
 
 
+def test_graph_cache_answers_a_failed_capture_eagerly_and_never_retries(cuda, lib):
+    """An exception leaving the capture: the call is answered by eager launches, the signature stays eager-only, nothing stays pinned
+    (hip._KEEP), and other signatures capture and replay as ever."""
+    from jatts_amd import hip
+    from jatts_amd.graphs import GraphCache
+    gc = GraphCache(max_graphs=2)
+    x = torch.arange(8, dtype=torch.float32, device=cuda)
+
+    def fn(t):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("not under capture")
+        return t * 2 + 1
+    for _ in range(3):
+        assert torch.equal(gc.run("a", fn, (x,)), x * 2 + 1)
+    assert gc.stats["failed"] == 1 and gc.stats["captured"] == 0 and gc._g["a"].get("eager_only") and len(gc) == 0
+    assert hip._KEEP[0] is None
+    for _ in range(3):
+        assert torch.equal(gc.run("b", lambda t: t * 2 + 1, (x,)), x * 2 + 1)
+    assert gc.stats == dict(eager=3, captured=1, replayed=1, failed=1) and len(gc) == 1
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # Replay after the process has done other work: the bounded upload caches evict, the conformer stacks' positional tables regrow.
 

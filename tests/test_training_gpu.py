@@ -899,3 +899,37 @@ def test_graph_replay_guard_trips_on_an_absurd_gradient_norm(cuda, lib):
     assert st.get("eager_only")
     tr.GRAD_NORM_SANITY = 1e12
     assert math.isfinite(float(tr.train_step(batch)["loss"]))      # the signature keeps training, eagerly
+
+
+def test_failed_step_capture_propagates_and_leaves_the_trainer_eager(cuda, lib, monkeypatch):
+    """An exception leaving the capture of a step (here: from compute_losses, before it launches anything) reaches the caller; nothing stays
+    pinned, every .grad is its flat view again, the model's graph-mode attributes are cleared, the signature is eager-only, and `steps` counts
+    only the steps that ran."""
+    from jatts_amd import hip
+    from jatts_amd.models import FastSpeech2
+    from jatts_amd.training import FastSpeech2Trainer
+    z, zi, keys, cfg = _train_golden()
+    t = lambda k: torch.tensor(zi[k])  # noqa: E731
+    il, ol = t("text_lengths"), t("feats_lengths")
+    batch = dict(xs=t("text"), ilens=il, ys=t("feats"), olens=ol, durations=t("durations"), duration_lens=il, pitch=t("pitch"),
+                 pitch_lens=il, energys=t("energy"), energy_lens=il)
+    m = FastSpeech2(idim=20, **{**FS2_SMALL, "stop_gradient_from_pitch_predictor": True, "use_masking": True})
+    m.load_state_dict(golden_state(keys, 0))
+    tr = FastSpeech2Trainer(m.to(cuda), lr=1e-3, grad_norm=1.0, warmup_steps=10, capture_graph=True)
+    views = [p.grad.data_ptr() for p in tr.params]
+    real = tr.compute_losses
+
+    def compute_losses(b):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("not under capture")
+        return real(b)
+    monkeypatch.setattr(tr, "compute_losses", compute_losses)
+    assert math.isfinite(float(tr.train_step(batch)["loss"])) and tr.steps == 1      # first sight: eager
+    with pytest.raises(RuntimeError, match="not under capture"):
+        tr.train_step(batch)
+    assert tr.steps == 1 and hip._KEEP[0] is None and tr.model._seed_dev is None and tr.model._static_olens is None
+    assert [p.grad.data_ptr() for p in tr.params] == views
+    (st,) = tr._graphs.values()
+    assert st.get("eager_only") and st.get("graph") is None
+    assert math.isfinite(float(tr.train_step(batch)["loss"])) and tr.steps == 2      # eagerly from now on
+    assert [p.grad.data_ptr() for p in tr.params] == views
