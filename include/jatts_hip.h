@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define JATTS_ABI_VERSION 7   /* (round 15 added jatts_stft_mag, jatts_logmel_post, jatts_energy_frames, jatts_energy_adjust and jatts_token_average without a bump, as rounds 10, 11 and 13 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 13: jatts_hifigan_resunit / jatts_resunit_variant take w2 == NULL as the single-conv dilation unit, without a bump: no descriptor or signature changed, and a library from before it lacks jatts_resunit_single_conv, so it is refused when _abi.load binds that symbol) (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
+#define JATTS_ABI_VERSION 7   /* (round 27 appended tap_group_n / tap_a0 / tap_b0 / tap_k to jatts_conv_desc WITHOUT a bump: the fields are a hint that every kernel may ignore, so a library from before them, which never reads that far, computes the same values; tests/test_attn_precision_cpu.py pins 7 -- a caller built against an older header must not be paired with this library: it would read the hint beyond the caller's struct) (round 15 added jatts_stft_mag, jatts_logmel_post, jatts_energy_frames, jatts_energy_adjust and jatts_token_average without a bump, as rounds 10, 11 and 13 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 13: jatts_hifigan_resunit / jatts_resunit_variant take w2 == NULL as the single-conv dilation unit, without a bump: no descriptor or signature changed, and a library from before it lacks jatts_resunit_single_conv, so it is refused when _abi.load binds that symbol) (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
                                 * so every descriptor that embeds it (jatts_conv_desc, jatts_resunit_desc, jatts_resblock_desc, jatts_relattn_desc) shifted by 8 bytes; JATTS_F32E; 2 (round 4): jatts_conv_desc + w_inv / act_a / act_b, jatts_resunit_desc + ws1 / ws2, jatts_resblock_desc + ws1 / ws2;
                                 * bumped whenever a descriptor's layout or an entry point's signature changes: a stale library is refused at load */
 
@@ -162,6 +162,18 @@ typedef struct jatts_conv_desc {
    * kernels); 1: [tap][c / 32][n / 16][lane = 16 ((c % 32) / 8) + n % 16][c % 8] x (b0 | b1 | b2) with n padded to 32 and c to 64 (v_mfma_f32_16x16x32_bf16 kernels,
    * csrc/conv1d_emul16.h: the form the power-limited matrix pipe sustains 14 % more of; jatts_amd.hip.pack_conv_weight_bf16x3_k32). */
   int32_t w_layout;
+  /* (round 27, appended without an ABI bump -- see JATTS_ABI_VERSION) A HINT about structural zeros in W -- the polyphase form of ConvTranspose1d(K = 2 stride) (jatts_amd.hip.convtranspose_as_conv) has k_w = 3 taps of
+   * which every output phase uses two.  tap_group_n = 0: no hint.  Otherwise the caller PROMISES W[n, :, tap] == 0 for n < tap_group_n outside
+   * [tap_a0, tap_a0 + tap_k) and for n >= tap_group_n outside [tap_b0, tap_b0 + tap_k).  The packed weight still holds all k_w taps, so a kernel that ignores
+   * the hint is correct: EVERY kernel ignores it except the 16 x 16 x 32 emulated conv (JATTS_F32E / JATTS_F32E6 with w_layout = 1), whose waves contract
+   * over their group's window only when tap_group_n is a multiple of the tile's per-wave channel span (else it too runs every tap).  The remaining
+   * products are summed in the same order, the skipped ones are +-0 for FINITE inputs: results are equal (==; a -0 may become +0).  With an Inf / NaN
+   * activation under a promised-zero tap the skipped 0 * Inf = NaN is not produced.  Refused (JATTS_ERR_ARG): tap_group_n < 0 or > n_out, tap_k < 1, a
+   * window outside [0, k_w], a hint together with n_split. */
+  int32_t tap_group_n;
+  int32_t tap_a0;
+  int32_t tap_b0;
+  int32_t tap_k;
 } jatts_conv_desc;
 
 int jatts_conv1d(const jatts_conv_desc* d, void* stream);

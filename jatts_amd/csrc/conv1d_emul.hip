@@ -46,11 +46,24 @@ static int conv1d_emul(const jatts_conv_desc& d, hipStream_t s) {
 //   2: 128 n x 128 t, eight waves of 2 x 4 fragments (anti-phase staging), one workgroup per CU
 //   1: 128 n x 64 t, four waves of 2 x 4 fragments, two workgroups per CU
 //   9: 128 n x 32 t, four waves of 2 x 2 fragments, two workgroups per CU
+// A launch with a tap-window hint (jatts_conv_desc.tap_group_n) keeps it only on a tile whose per-wave channel span NF * 16 divides tap_group_n: every wave then
+// lies in one group (the kernel picks the window from its first channel).  Otherwise the hint is cleared and every tap runs -- same values.
+template <typename T, int NF, int NT, int WN, int WT, int NIN, int KCHT, int OCC, int HALO = 32, int D = 2>
+static int launch_hinted16(const jatts_conv_desc& d, hipStream_t s) {
+  static_assert((KCHT / 32) % D == 0, "any tap count keeps the ring-depth rule");
+  if (d.tap_group_n == 0 || d.tap_group_n % (NF * 16) == 0) return launch_conv_emul16<T, NF, NT, WN, WT, NIN, KCHT, OCC, HALO, D>(d, s);
+  jatts_conv_desc u = d;
+  u.tap_group_n = u.tap_a0 = u.tap_b0 = u.tap_k = 0;
+  return launch_conv_emul16<T, NF, NT, WN, WT, NIN, KCHT, OCC, HALO, D>(u, s);
+}
+
 template <typename T>
 static int conv1d_emul16(const jatts_conv_desc& d, hipStream_t s) {
   const int variant = d.variant;
-  if (d.n_in > 1) return launch_conv_emul16<T, 4, 4, 2, 2, 3, 64, 1>(d, s);           // summed inputs (rare): 128 n x 128 t, four waves, one workgroup per CU
-  if (d.n_out <= 64) return launch_conv_emul16<T, 2, 2, 2, 2, 1, 64, 2>(d, s);        // 64 n x 64 t, four waves, two workgroups per CU: the HBM-bound last upsampling conv
+  // summed inputs (rare): 128 n x 128 t, four waves, one workgroup per CU.  Wave spans of 64: a hinted launch with a narrower group boundary (HiFi-GAN's last
+  // upsampling conv, tap_group_n = 32, whenever it is fed an unfused MRF sum) runs every tap here
+  if (d.n_in > 1) return launch_hinted16<T, 4, 4, 2, 2, 3, 64, 1>(d, s);
+  if (d.n_out <= 64) return launch_hinted16<T, 2, 2, 2, 2, 1, 64, 2>(d, s);           // 64 n x 64 t, four waves, two workgroups per CU: the HBM-bound last upsampling conv
   const int64_t maxL = (int64_t)d.rg.max_len * d.rg.len_mul;
   const int64_t t64 = ((maxL + 63) / 64) * d.rg.n_seq;                                // 64-row time tiles of the launch
   const int64_t wgs128 = ((maxL + 127) / 128) * d.rg.n_seq * ((d.n_out + 127) / 128);
@@ -61,20 +74,25 @@ static int conv1d_emul16(const jatts_conv_desc& d, hipStream_t s) {
   // instead of three times), 384 -> 1536 k3 184 -> 194, 2048 -> 512 k1 127 -> 146 TFLOP/s (profiles/r06_conv16_384_tile.txt, r06_conv16_wide_tiles.txt).
   // Conditions: n_out in whole tiles (a 384-wide output on 256-wide tiles leaves a quarter of the second one idle: -16 .. -21 %), at least one round of such
   // workgroups (fewer lose 13 - 15 %), and -- a two-output Q | K | V launch splits between workgroups -- n_split in whole tiles (jatts_conv1d checks whole 256s).
-  const bool ok384 = d.n_split % 384 == 0;
-  if (ok384 && (variant == 6 || (variant == 0 && d.n_out % 384 == 0 && t64 * (d.n_out / 384) >= 256))) return launch_conv_emul16<T, 3, 4, 8, 1, 1, 64, 1, 32, 1>(d, s);
-  if (variant == 3 || (variant == 0 && d.n_out % 256 == 0 && t64 * (d.n_out / 256) >= 256)) return launch_conv_emul16<T, 2, 4, 8, 1, 1, 64, 1>(d, s);
+  // (a hinted launch whose group boundary is no multiple of the 384-wide tile's 48-channel wave span goes on to the 256-wide tile, spans of 32, and keeps its hint)
+  const bool ok384 = d.n_split % 384 == 0 && (variant == 6 || d.tap_group_n % 48 == 0);
+  if (ok384 && (variant == 6 || (variant == 0 && d.n_out % 384 == 0 && t64 * (d.n_out / 384) >= 256))) return launch_hinted16<T, 3, 4, 8, 1, 1, 64, 1, 32, 1>(d, s);
+  if (variant == 3 || (variant == 0 && d.n_out % 256 == 0 && t64 * (d.n_out / 256) >= 256)) return launch_hinted16<T, 2, 4, 8, 1, 1, 64, 1>(d, s);
   // (measured and dropped, evidence under profiles/: 192 n x 64 t two workgroups per CU -- r06_conv16_192_tile.txt; 512 n x 32 t -- r06_conv16_512_tile.txt: twice
   //  the weight bytes per MFMA cost what half the staging saved; the 256-wide tile with the one-step ring: +-2 %; four-wave tiles of 4 x 4 fragments, one wave per
   //  SIMD, 256 n x 64 t and 128 n x 128 t: -8 .. -25 % -- r06_conv16_wide_tiles.txt; 64 n x 32 t for one utterance: behind 128 n x 32 t -- r06_conv16_b1_tiles.txt)
   // ONE-UTTERANCE launches (the B = 1 drop-in path: 768 rows): even the 128 n x 64 t tile leaves most CUs idle -- 36 workgroups for a 1536 -> 384 conv, each
   // walking 144 K-steps.  128 n x 32 t when the 64-row tiling gives at most one workgroup per CU: 1536 -> 384 k3 110 -> 67 us, 384 -> 1536 k3 35 -> 29 us,
   // 384 -> 384 k1 16 -> 12 us; b1_latency 8.6 -> 7.55 ms (profiles/r06_conv16_b1_tiles.txt)
-  if (variant == 9 || (variant == 0 && t64 * ((d.n_out + 127) / 128) <= 256)) return launch_conv_emul16<T, 2, 2, 4, 1, 1, 64, 2>(d, s);
+  if (variant == 9 || (variant == 0 && t64 * ((d.n_out + 127) / 128) <= 256)) return launch_hinted16<T, 2, 2, 4, 1, 1, 64, 2>(d, s);
   // 128 n x 64 t, two workgroups per CU: k = 1 (the eight-wave 128 x 128 tile halves the weight traffic -- 1.56 - 1.76 GHz -- but converts with the pipe idle; the
   // anti-phase staging gives it +3 - 5 % at k = 1, still behind this tile), and launches that cannot give every CU a 128 x 128 workgroup
-  if (variant == 1 || (variant == 0 && (d.k_w == 1 || wgs128 <= 128))) return launch_conv_emul16<T, 2, 4, 4, 1, 1, 64, 2>(d, s);
-  return launch_conv_emul16<T, 2, 4, 4, 2, 1, 64, 1>(d, s);                           // 128 n x 128 t, eight waves, one workgroup per CU
+  // (round 27) ... and launches that keep a tap-window hint here (two real taps of three: four K-steps per chunk, so staging weighs more): the second workgroup's
+  // MFMAs cover the first one's staging -- 128 -> 128 at 3.1 M rows 1.66 -> 1.52 ms, 256 -> 640 at 246 K rows 1.09 -> 1.00 ms, 64 -> 96 at 4.9 M rows
+  // 1.46 -> 1.36 ms against the 128 x 128 tile (profiles/r27_notes.md; tools/bench_upsample.py)
+  const bool hinted = d.tap_group_n > 0 && d.tap_group_n % 32 == 0;
+  if (variant == 1 || (variant == 0 && (d.k_w == 1 || wgs128 <= 128 || hinted))) return launch_hinted16<T, 2, 4, 4, 1, 1, 64, 2>(d, s);
+  return launch_hinted16<T, 2, 4, 4, 2, 1, 64, 1>(d, s);                           // 128 n x 128 t, eight waves, one workgroup per CU
 }
 
 int jatts_conv1d_emul(const jatts_conv_desc& d, hipStream_t s) {

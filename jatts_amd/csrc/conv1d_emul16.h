@@ -272,7 +272,15 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void conv1d_emul16_kernel(jatts_c
   static_assert((KCHT / 32) % D == 0 || D % (KCHT / 32) == 0, "ring depth and steps per chunk and tap");
   WRing16<T, NF, D> ring;
   const int n_chunks = d.c_in / KCHT;
-  ring.init((const T*)d.w, KC32, NFR16, nf0, d.k_w, KCHT / 32, n_chunks, lane);
+  // The tap-window hint (jatts_conv_desc.tap_group_n; the dispatcher passes it on only where this tile's per-wave channel span NF * 16 divides it, so a wave
+  // lies in ONE group): the wave walks its group's tap_k real taps -- the ring bound at tap tap0 (the weights are tap-major), the B fragments read tap0 * dil
+  // rows further down the staged tile.  Staging, rows, barriers and the chunk -> tap -> K-step order are those of the unhinted launch; both groups run the same
+  // number of K-steps.  No hint: tap0 = 0, kw = k_w.
+  const bool hinted = d.tap_group_n > 0;
+  const int tap0 = __builtin_amdgcn_readfirstlane(hinted ? (nf0 * 16 < d.tap_group_n ? d.tap_a0 : d.tap_b0) : 0);
+  const int kw = hinted ? d.tap_k : d.k_w;
+  const size_t tap_off = (size_t)(tap0 * d.dil) * pitch;
+  ring.init((const T*)d.w + (size_t)tap0 * KC32 * NFR16 * 512, KC32, NFR16, nf0, kw, KCHT / 32, n_chunks, lane);
   const size_t buf_bytes = (size_t)rows * pitch;
   StageRegs<float, MAXU, NIN> sr;
   // the staging plan: a unit's row does not change from chunk to chunk -- offsets and masks once (round 6: "issue loads" was 3.5 - 8 % of a workgroup's life)
@@ -320,7 +328,7 @@ __global__ __launch_bounds__(WN* WT * 64, OCC) void conv1d_emul16_kernel(jatts_c
       if (ci + 2 < n_chunks) issue((ci + 2) * KCHT);
     } else if (more && !(JATTS_CEMUL_DIAG & 2)) issue((ci + 1) * KCHT);
     JATTS_PH(1);    // issue of the next chunk's loads (early waves: the commit too)
-    conv_stage16<T, NF, NT, D>(accx, ring, KCHT / 32, d.k_w, d.dil, smem + (size_t)(ci & 1) * buf_bytes, pitch, col0, lane);
+    conv_stage16<T, NF, NT, D>(accx, ring, KCHT / 32, kw, d.dil, smem + (size_t)(ci & 1) * buf_bytes + tap_off, pitch, col0, lane);
     JATTS_PH(2);    // K-steps
 #if JATTS_CEMUL_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -58,6 +58,10 @@ extern "C" int jatts_conv1d(const jatts_conv_desc* d, void* stream) {
     return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d: JATTS_ACT_SNAKEBETA needs 16-byte aligned act_a / act_b and n_out % 4 == 0");
   if (d->n_split != 0 && (d->n_split < 0 || d->n_split % 256 || d->n_split >= d->n_out || !d->y2 || d->y_transposed || d->resid || d->ldy2 <= 0))
     return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d: n_split must be a multiple of 256 below n_out, with y2 / ldy2 set, y row-major and no residual");
+  // the tap-window hint (a promise about zeros in W; kernels may ignore it): both windows inside [0, k_w], one output
+  if (d->tap_group_n != 0 && (d->tap_group_n < 0 || d->tap_group_n > d->n_out || d->tap_k < 1 || d->tap_a0 < 0 || d->tap_b0 < 0 ||
+                              (int64_t)d->tap_a0 + d->tap_k > d->k_w || (int64_t)d->tap_b0 + d->tap_k > d->k_w || d->n_split != 0))
+    return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d: tap window: 0 < tap_group_n <= n_out, tap_k >= 1, both windows inside [0, k_w], no n_split");
   if (d->w_layout != 0 && d->dtype != JATTS_F32E && d->dtype != JATTS_F32E6) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d: w_layout = 1 goes with JATTS_F32E / JATTS_F32E6 only");
   if (d->rg.max_len <= 0) return JATTS_OK;
   hipStream_t s = (hipStream_t)stream;

@@ -604,13 +604,49 @@ def pack_conv_weight_bf16x3_dev(w, c_mult=64, dgrad=False):
     return out, c_pad
 
 
+def _polyphase_taps(K, stride, padding):
+    """The (phase r, input offset q) pairs of ConvTranspose1d(K, stride, padding): output step j * stride + r takes w[..., stride * q + r + padding] from
+    input row j - q.  -> (pairs, qmin, qmax); the polyphase conv holds the pair (r, q) at tap qmax - q."""
+    qs = [(r, q) for r in range(stride) for q in range(-K, K + 1) if 0 <= stride * q + r + padding < K]
+    return qs, min(q for _, q in qs), max(q for _, q in qs)
+
+
+def convtranspose_tap_groups(K, stride, padding):
+    """The tap windows of convtranspose_as_conv's weight, from its structure alone (never from weight values): the phases' real taps are a contiguous
+    window each; when the phases 0 .. a - 1 share one window, the phases a .. stride - 1 another, and both are equally long,
+    -> (a, first tap of group A, first tap of group B, taps per group) -- with c_out output channels per phase, jatts_conv_desc's tap_group_n = a * c_out,
+    tap_a0, tap_b0, tap_k.  K = 2 stride: two taps each, {0, 1} then {1, 2}.  Any other pattern (one window for every phase, three windows, unequal
+    lengths, holes) -> None."""
+    qs, _, qmax = _polyphase_taps(K, stride, padding)
+    wins = []
+    for r in range(stride):
+        taps = sorted(qmax - q for rr, q in qs if rr == r)
+        if not taps or taps != list(range(taps[0], taps[-1] + 1)):
+            return None
+        wins.append((taps[0], len(taps)))
+    a = next((r for r in range(stride) if wins[r] != wins[0]), stride)
+    if a == stride or any(wn != wins[a] for wn in wins[a:]) or wins[0][1] != wins[a][1]:
+        return None
+    return a, wins[0][0], wins[a][0], wins[0][1]
+
+
+def check_tap_window(wc, tap_window):
+    """Raises ValueError unless the dense conv weight wc (n_out, c_in, k_w) is zero outside tap_window = (tap_group_n, tap_a0, tap_b0, tap_k): the promise
+    jatts_conv_desc's hint makes (callers check ONCE, when they pack the weight)."""
+    n, a0, b0, k = tap_window
+    keep = torch.zeros(wc.shape[0], wc.shape[2], dtype=torch.bool, device=wc.device)
+    keep[:n, a0:a0 + k] = True
+    keep[n:, b0:b0 + k] = True
+    if bool((wc != 0).any(1)[~keep].any()):
+        raise ValueError(f"tap window {tuple(tap_window)}: the weight is not zero outside it")
+
+
 def convtranspose_as_conv(w, stride, padding):
     """ConvTranspose1d weight (c_in, c_out, K) -> polyphase Conv1d weight
     (stride*c_out, c_in, taps) + input offset `pad`, such that the conv output row j,
     viewed as [stride][c_out], equals output steps j*stride .. j*stride+stride-1."""
     c_in, c_out, K = w.shape
-    qs = [(r, q) for r in range(stride) for q in range(-K, K + 1) if 0 <= stride * q + r + padding < K]
-    qmin, qmax = min(q for _, q in qs), max(q for _, q in qs)
+    qs, qmin, qmax = _polyphase_taps(K, stride, padding)
     taps = qmax - qmin + 1
     wc = torch.zeros(stride * c_out, c_in, taps, dtype=w.dtype, device=w.device)
     for r, q in qs:
@@ -622,13 +658,14 @@ def convtranspose_as_conv(w, stride, padding):
 def conv1d(rb, xs, w_packed, c_in, n_out, k_w, *, dtype, dil=1, pad=None, bias=None, act=ACT_NONE,
            alpha=1.0, resid=None, out=None, out_f32=False, transposed=False, pre_lrelu=None,
            in_scale=1.0, ldx=None, x_col0=0, len_mul=1, out_ld=None, out_col0=0, out_rows=None, resid_col0=0,
-           y_seq_col0=None, reflect=False, variant=0, w_inv=None, snake=None, split=None, w_layout=0):
+           y_seq_col0=None, reflect=False, variant=0, w_inv=None, snake=None, split=None, w_layout=0, tap_window=None):
     """See jatts_conv1d in include/jatts_hip.h.  ``xs`` is a tensor or list of <=3 tensors.  dtype F32S: f32 tensors, ``w_packed`` / ``w_inv``
     from pack_conv_weight_split (c_mult 64).  ``snake`` = (exp(alpha), 1 / (exp(beta) + 1e-9)) f32 vectors of n_out: the SnakeBeta
     activation (the ``snakebeta`` op) applied in the epilogue instead of ``act``.  ``split`` = (n_split, ld2, seq_col0): TWO outputs from one launch
     (the Q | K | V projection): channels < n_split row-major as usual, channels >= n_split transposed into a (n_out - n_split, ld2) matrix with the V^T
     column layout ``seq_col0`` (RaggedBatch.vt_layout); returns (out, out2).  ``pad`` (default: the "same" offset (k_w - 1) // 2 * dil) must lie in
-    [0, (k_w - 1) * dil]; the library refuses anything else."""
+    [0, (k_w - 1) * dil]; the library refuses anything else.  ``tap_window`` = (tap_group_n, tap_a0, tap_b0, tap_k): the caller's PROMISE that the weight
+    is zero outside those taps (jatts_conv_desc.tap_group_n: a hint, same result with or without; check_tap_window verifies a dense weight)."""
     lib = _abi.load()
     if isinstance(xs, torch.Tensor):
         xs = [xs]
@@ -707,6 +744,8 @@ def conv1d(rb, xs, w_packed, c_in, n_out, k_w, *, dtype, dil=1, pad=None, bias=N
     d.w_layout = w_layout if dtype in EMUL else 0
     if out2 is not None:
         d.n_split, d.ldy2, d.y2, d.y2_seq_col0 = split[0], split[1], out2.data_ptr(), _ptr(split[2])
+    if tap_window is not None:
+        d.tap_group_n, d.tap_a0, d.tap_b0, d.tap_k = tap_window
     _count(2.0 * c_in * n_out * k_w * rows)
     with _Timed("conv1d", (c_in, n_out, k_w, rows)):
         _abi.check(lib.jatts_conv1d(C.byref(d), _stream()), "jatts_conv1d")

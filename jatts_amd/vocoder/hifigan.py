@@ -176,8 +176,14 @@ class HiFiGANGenerator(Prepared, torch.nn.Module):
             wp = torch.zeros(c_prev, c_out, w.shape[2], dtype=torch.float32)
             wp[: w.shape[0], : w.shape[1]] = w
             wc, pad = hip.convtranspose_as_conv(wp, s, s // 2 + s % 2)
+            # every phase of the polyphase weight has K / s = 2 real taps out of 3: the window goes with every launch as a hint (jatts_conv_desc.tap_group_n;
+            # the emulated 16 x 16 x 32 conv contracts over the real taps only), checked against the dense weight here, once
+            tg = hip.convtranspose_tap_groups(uk, s, s // 2 + s % 2)
+            win = None if tg is None else (tg[0] * c_out,) + tg[1:]
+            if win is not None:
+                hip.check_tap_window(wc, win)
             pc = PackedConv(wc, padb(sd.get(f"upsamples.{i}.1.bias"), c_out).repeat(s), dt, dev)
-            P["ups"].append((pc, pad, s, c_out))
+            P["ups"].append((pc, pad, s, c_out, win))
             stage = []
             for j, rk in enumerate(self.resblock_kernel_sizes):
                 units = []
@@ -247,10 +253,10 @@ class HiFiGANGenerator(Prepared, torch.nn.Module):
             taps["input_conv"] = x.float()
         xs, in_scale, rate = [x], 1.0, 1
         supported = P["unit_channels"]
-        for i, (pc, pad, s, c_out) in enumerate(P["ups"]):
+        for i, (pc, pad, s, c_out, win) in enumerate(P["ups"]):
             rows = rb.total * rate
             up = hip.conv1d(rb, xs, pc.w, pc.c_in, pc.n_out, pc.k, dtype=dt, bias=pc.b, pad=pad,
-                            pre_lrelu=self.slope, in_scale=in_scale, len_mul=rate)       # (rows, s*c_out)
+                            pre_lrelu=self.slope, in_scale=in_scale, len_mul=rate, tap_window=win)       # (rows, s*c_out)
             rate *= s
             up = up.view(rows * s, c_out)
             if taps is not None:
