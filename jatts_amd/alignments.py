@@ -7,7 +7,7 @@ launch (jatts_mas_viterbi) and nothing leaves the GPU.
 import torch
 
 from . import hip
-from .models._conformer import PackedConv
+from .hip import PackedConv
 
 
 class AlignmentModule(torch.nn.Module):
@@ -57,8 +57,7 @@ class AlignmentModule(torch.nn.Module):
                 xp = torch.zeros(x.shape[0], c_in, dtype=torch.float32, device=x.device)
                 xp[:, : x.shape[1]] = x
                 x = xp
-            return hip.conv1d(rb, x.contiguous(), p.w, c_in, p.n_out, p.k, dtype=hip.F32, bias=p.b,
-                              act=hip.ACT_RELU if relu else hip.ACT_NONE)
+            return p(rb, x.contiguous(), act=hip.ACT_RELU if relu else hip.ACT_NONE)
         t = conv(rb_t, conv(rb_t, text.float(), "t_conv1", True), "t_conv2", False)
         f = conv(rb_f, conv(rb_f, conv(rb_f, feats.float(), "f_conv1", True), "f_conv2", True), "f_conv3", False)
         return hip.alignment_logp(rb_f, rb_t, f, t, self.adim)
@@ -107,7 +106,7 @@ def padded_alignment(convs, hs, ys, ilens, olens, adim):
         pc = convs[n]
         if x.shape[1] != pc.c_in:
             x = hip.affine_cast(x, hip.F32, ldy=pc.c_in)
-        return hip.conv1d(rb, x, pc.w, pc.c_in, pc.n_out, pc.k, dtype=hip.F32, bias=pc.b, act=hip.ACT_RELU if relu else hip.ACT_NONE)
+        return pc(rb, x, act=hip.ACT_RELU if relu else hip.ACT_NONE)
     rbt, rbf = hip.RaggedBatch([Tm] * B, dev), hip.RaggedBatch([To] * B, dev)
     tf = conv(rbt, conv(rbt, hs, "t_conv1", True), "t_conv2", False)
     ff = conv(rbf, conv(rbf, conv(rbf, ys.reshape(B * To, od).contiguous(), "f_conv1", True), "f_conv2", True), "f_conv3", False)

@@ -147,13 +147,14 @@ class LogMelExtractor:
         self.num_mels, self.eps = int(num_mels), float(eps)
         self.ld_out = hip.round_up(self.num_mels, 64)
         mel = mel_filterbank(sampling_rate, self.n_fft, self.num_mels, fmin, fmax)            # (n_bins, n_mels)
-        self.mel_w = hip.pack_conv_weight(torch.from_numpy(mel.T.copy()).float().unsqueeze(-1).to(self.device), F32, 64)
+        with hip.operands(None):     # exact f32 always
+            self.mel_w = hip.PackedConv(torch.from_numpy(mel.T.copy()), None, F32, self.device)     # c_in = stft.ld_mag
 
     @torch.no_grad()
     def mel(self, waves):
         """-> (RaggedBatch over frames, linear mel spectrogram f32 (rows, num_mels)): np.dot(spc, mel_basis.T) of mel.py:64."""
         rb, mag, _ = self.stft.magnitude(PackedWaves.from_list(waves, self.device))
-        return rb, hip.conv1d(rb, mag, self.mel_w, self.stft.ld_mag, self.num_mels, 1, dtype=F32)
+        return rb, self.mel_w(rb, mag)
 
     @torch.no_grad()
     def __call__(self, waves):

@@ -562,6 +562,34 @@ def f32_operand(w, c_mult=64):
     return operand(_OPERAND[0], w, c_mult)
 
 
+class PackedConv:
+    """A Conv1d/Linear layer prepared for jatts_conv1d: the packed operand ``w``, the folded bias ``b``, the geometry (``c_in`` padded to c_mult,
+    ``n_out``, ``k``) and the tensor dtype code it was packed for.  Calling it is the launch: ``layer(rb, xs, act=..., resid=..., out=...)``."""
+
+    def __init__(self, w, b, dtype, device, scale=None, shift=None, c_mult=64):
+        # w: (n, c, k) or (n, c); optional per-output-channel affine folded in (BatchNorm eval)
+        w = w.detach().float()
+        if w.dim() == 2:
+            w = w.unsqueeze(-1)
+        b = None if b is None else b.detach().float()
+        if scale is not None:
+            w = w * scale.view(-1, 1, 1)
+            b = (b * scale if b is not None else torch.zeros_like(scale)) + shift
+        self.dtype = dtype
+        self.n_out, c, self.k = w.shape
+        self.c_in = round_up(c, c_mult)
+        # set_precision("fp32_split"): f32 tensors, split f16 hi/lo MFMA operands (hip.operands is on while the model prepares)
+        # set_precision("fp32_bf16x3"): f32 tensors, three exact bf16 terms per operand, seven (fp32_bf16x3_6p: six) MFMA products (EmulWeight)
+        self.w = f32_operand(w.to(device), c_mult) if dtype == F32 else pack_conv_weight(w.to(device), dtype, c_mult)
+        self.b = None if b is None else b.to(device).contiguous()
+
+    def __call__(self, rb, xs, **kw):
+        """hip.conv1d on this layer: the keywords are the launch's own (inputs' layout, activation, residual, output placement); ``bias=`` overrides
+        the folded bias (None: launch without one)."""
+        kw.setdefault("bias", self.b)
+        return conv1d(rb, xs, self.w, self.c_in, self.n_out, self.k, dtype=self.dtype, **kw)
+
+
 def _pack_dev_args(w, c_mult, dgrad):
     """The shared opening of the device packers: -> (library, contiguous f32 device weight, its (n, c, k), padded n_out and c_in of the packed conv)."""
     lib = _abi.load()

@@ -41,26 +41,6 @@ def rel_pos_table_new(cap, d):
     return pe
 
 
-class PackedConv:
-    """A Conv1d/Linear weight packed for jatts_conv1d."""
-
-    def __init__(self, w, b, dtype, device, scale=None, shift=None, c_mult=64):
-        # w: (n, c, k) or (n, c); optional per-output-channel affine folded in (BatchNorm eval)
-        w = w.detach().float()
-        if w.dim() == 2:
-            w = w.unsqueeze(-1)
-        b = None if b is None else b.detach().float()
-        if scale is not None:
-            w = w * scale.view(-1, 1, 1)
-            b = (b * scale if b is not None else torch.zeros_like(scale)) + shift
-        self.n_out, c, self.k = w.shape
-        self.c_in = hip.round_up(c, c_mult)
-        # set_precision("fp32_split"): f32 tensors, split f16 hi/lo MFMA operands (hip.operands is on while the model prepares)
-        # set_precision("fp32_bf16x3"): f32 tensors, three exact bf16 terms per operand, seven (fp32_bf16x3_6p: six) MFMA products (hip.EmulWeight)
-        self.w = hip.f32_operand(w.to(device), c_mult) if dtype == hip.F32 else hip.pack_conv_weight(w.to(device), dtype, c_mult)
-        self.b = None if b is None else b.to(device).contiguous()
-
-
 class SpkProjection:
     """_integrate_with_spk_embed (models/fastspeech2.py:737-761; the same method in matchatts.py:560-584, matchatts_mas.py:644-668,
     vits.py:681-705).  "add": hs += projection(normalize(spembs)).  "concat": projection(cat[hs, normalize(spembs) broadcast over time])
@@ -73,20 +53,20 @@ class SpkProjection:
         w, b = sd["projection.weight"], sd["projection.bias"]
         self.kind, self.A, self.dtype = kind, adim, dtype
         if kind == "add":
-            self.h, self.s = None, PackedConv(w, b, dtype, device)
+            self.h, self.s = None, hip.PackedConv(w, b, dtype, device)
         else:
             if w.shape[1] <= adim:
                 raise ValueError("projection.weight: 'concat' expects (adim, adim + spk_embed_dim)")
-            self.h, self.s = PackedConv(w[:, :adim], None, dtype, device), PackedConv(w[:, adim:], b, dtype, device)
+            self.h, self.s = hip.PackedConv(w[:, :adim], None, dtype, device), hip.PackedConv(w[:, adim:], b, dtype, device)
 
     def __call__(self, rb, hs, spembs):
         """hs: f32 (rows, adim) of the ragged batch rb; spembs: (n_seq, D).  -> hs with the speaker integrated (in place for "add")."""
         dev, B = hs.device, rb.n_seq
         rbs = hip.RaggedBatch([1] * B, dev)
         sp = hip.l2_normalize(spembs.to(dev).float().reshape(B, -1).contiguous(), self.dtype, ldy=self.s.c_in)
-        vec = hip.conv1d(rbs, sp, self.s.w, self.s.c_in, self.A, 1, dtype=self.dtype, bias=self.s.b, out_f32=True)
+        vec = self.s(rbs, sp, out_f32=True)
         if self.h is not None:
-            hs = hip.conv1d(rb, hip.affine_cast(hs, self.dtype), self.h.w, self.h.c_in, self.A, 1, dtype=self.dtype, out_f32=True)
+            hs = self.h(rb, hip.affine_cast(hs, self.dtype), out_f32=True)
         hip.add_seq_vector(rb, hs, vec)
         return hs
 
@@ -120,27 +100,27 @@ class ConformerRunner:
                     L[nm] = (f32(g(p + nm + ".weight")), f32(g(p + nm + ".bias")))
             for ff in ("feed_forward", "feed_forward_macaron"):
                 if has(ff + ".w_1.weight"):
-                    L[ff] = (PackedConv(g(p + ff + ".w_1.weight"), g(p + ff + ".w_1.bias"), dtype, device),
-                             PackedConv(g(p + ff + ".w_2.weight"), g(p + ff + ".w_2.bias"), dtype, device))
+                    L[ff] = (hip.PackedConv(g(p + ff + ".w_1.weight"), g(p + ff + ".w_1.bias"), dtype, device),
+                             hip.PackedConv(g(p + ff + ".w_2.weight"), g(p + ff + ".w_2.bias"), dtype, device))
             a = p + "self_attn."
             wq, wk = g(a + "linear_q.weight"), g(a + "linear_k.weight")
             if (2 * self.A) % 256 == 0:     # Q | K | V as ONE launch (jatts_conv_desc.n_split): Q | K row-major, V transposed
-                L["qkv"] = PackedConv(torch.cat([wq, wk, g(a + "linear_v.weight")], 0),
+                L["qkv"] = hip.PackedConv(torch.cat([wq, wk, g(a + "linear_v.weight")], 0),
                                       torch.cat([g(a + "linear_q.bias"), g(a + "linear_k.bias"), g(a + "linear_v.bias")], 0), dtype, device)
             else:                           # Q | K and V as two launches
-                L["qk"] = PackedConv(torch.cat([wq, wk], 0), torch.cat([g(a + "linear_q.bias"), g(a + "linear_k.bias")], 0),
+                L["qk"] = hip.PackedConv(torch.cat([wq, wk], 0), torch.cat([g(a + "linear_q.bias"), g(a + "linear_k.bias")], 0),
                                      dtype, device)
-                L["v"] = PackedConv(g(a + "linear_v.weight"), g(a + "linear_v.bias"), dtype, device)
-            L["o"] = PackedConv(g(a + "linear_out.weight"), g(a + "linear_out.bias"), dtype, device)
+                L["v"] = hip.PackedConv(g(a + "linear_v.weight"), g(a + "linear_v.bias"), dtype, device)
+            L["o"] = hip.PackedConv(g(a + "linear_out.weight"), g(a + "linear_out.bias"), dtype, device)
             L["rel"] = has("self_attn.linear_pos.weight")
             if L["rel"]:
-                L["pos"] = PackedConv(g(a + "linear_pos.weight"), None, dtype, device)
+                L["pos"] = hip.PackedConv(g(a + "linear_pos.weight"), None, dtype, device)
                 L["u"] = f32(g(a + "pos_bias_u"))
                 L["vb"] = f32(g(a + "pos_bias_v"))
             if has("conv_module.pointwise_conv1.weight"):
                 c = p + "conv_module."
-                L["pw1"] = PackedConv(g(c + "pointwise_conv1.weight"), g(c + "pointwise_conv1.bias"), dtype, device)
-                L["pw2"] = PackedConv(g(c + "pointwise_conv2.weight"), g(c + "pointwise_conv2.bias"), dtype, device)
+                L["pw1"] = hip.PackedConv(g(c + "pointwise_conv1.weight"), g(c + "pointwise_conv1.bias"), dtype, device)
+                L["pw2"] = hip.PackedConv(g(c + "pointwise_conv2.weight"), g(c + "pointwise_conv2.bias"), dtype, device)
                 wd = g(c + "depthwise_conv.weight").detach().float()
                 L["dw_w"] = f32(wd.reshape(wd.shape[0], wd.shape[-1]))
                 s = g(c + "norm.weight").detach().float() / torch.sqrt(g(c + "norm.running_var").detach().float() + BN_EPS)
@@ -181,7 +161,7 @@ class ConformerRunner:
             if not L["rel"]:
                 per_layer.append(None)
                 continue
-            P = hip.conv1d(rb, pe_t, L["pos"].w, L["pos"].c_in, self.A, 1, dtype=self.dtype)  # (cap, A)
+            P = L["pos"](rb, pe_t)                                                             # (cap, A)
             cv = hip.rowdot(P, self.A, n_pos, self.H, self.dk, L["vb"]).t().contiguous()      # (H, n_pos)
             # per-head weight operand of the BD GEMM (n = position m, contraction d_k): pure re-layout
             heads = [hip.operand(self.operand, P[:, h * self.dk:(h + 1) * self.dk].float().unsqueeze(-1)) for h in range(self.H)]
@@ -194,20 +174,17 @@ class ConformerRunner:
     def _ffn(self, rb, x, ln, ff, scale):
         xn = hip.layernorm(x, ln[0], ln[1], self.dtype, LN_EPS)
         w1, w2 = ff
-        h = hip.conv1d(rb, xn, w1.w, w1.c_in, w1.n_out, w1.k, dtype=self.dtype, bias=w1.b, act=ACT_RELU)
-        hip.conv1d(rb, h, w2.w, w2.c_in, w2.n_out, w2.k, dtype=self.dtype, bias=w2.b, act=ACT_NONE,
-                   alpha=scale, resid=x, out=x, out_f32=True)
+        w2(rb, w1(rb, xn, act=ACT_RELU), act=ACT_NONE, alpha=scale, resid=x, out=x, out_f32=True)
 
     def _mha(self, rb, x, L, pos, kv_len=None):
         A, H, dk = self.A, self.H, self.dk
         xn = hip.layernorm(x, L["norm_mha"][0], L["norm_mha"][1], self.dtype, LN_EPS)
         vcol, ldvt = rb.vt_layout()
         if "qkv" in L:
-            qk, vt = hip.conv1d(rb, xn, L["qkv"].w, A, 3 * A, 1, dtype=self.dtype, bias=L["qkv"].b, split=(2 * A, ldvt, vcol))   # (R, 2A), (A, ldvt)
+            qk, vt = L["qkv"](rb, xn, split=(2 * A, ldvt, vcol))                             # (R, 2A), (A, ldvt)
         else:
-            qk = hip.conv1d(rb, xn, L["qk"].w, A, 2 * A, 1, dtype=self.dtype, bias=L["qk"].b)       # (R, 2A)
-            vt = hip.conv1d(rb, xn, L["v"].w, A, A, 1, dtype=self.dtype, bias=L["v"].b, transposed=True,
-                            out_ld=ldvt, y_seq_col0=vcol)                                            # (A, ldvt)
+            qk = L["qk"](rb, xn)                                                             # (R, 2A)
+            vt = L["v"](rb, xn, transposed=True, out_ld=ldvt, y_seq_col0=vcol)               # (A, ldvt)
         g = ku = None
         ldg = 0
         rel_mode, rel_center = 1, 0
@@ -225,14 +202,13 @@ class ConformerRunner:
         ctx = hip.relpos_attention(rb, qk, 2 * A, qk, 2 * A, vt, ldvt, g, ldg, ku, 1.0 / math.sqrt(dk),
                                    H, dk, hip.attention_dtype(self.dtype, self.split, self.attn, H, dk, rel_mode), q_col0=0, k_col0=A, rel_mode=rel_mode, rel_center=rel_center, vt_col0=vcol,
                                    kv_len=kv_len)
-        hip.conv1d(rb, ctx, L["o"].w, A, A, 1, dtype=self.dtype, bias=L["o"].b, resid=x, out=x, out_f32=True)
+        L["o"](rb, ctx, resid=x, out=x, out_f32=True)
 
     def _convmod(self, rb, x, L):
-        A = self.A
         xn = hip.layernorm(x, L["norm_conv"][0], L["norm_conv"][1], self.dtype, LN_EPS)
-        pw = hip.conv1d(rb, xn, L["pw1"].w, A, 2 * A, 1, dtype=self.dtype, bias=L["pw1"].b)
-        dw = hip.glu_dwconv_bn_swish(rb, pw, A, L["dw_k"], L["dw_w"], L["dw_s"], L["dw_t"], self.dtype)
-        hip.conv1d(rb, dw, L["pw2"].w, A, A, 1, dtype=self.dtype, bias=L["pw2"].b, resid=x, out=x, out_f32=True)
+        pw = L["pw1"](rb, xn)
+        dw = hip.glu_dwconv_bn_swish(rb, pw, self.A, L["dw_k"], L["dw_w"], L["dw_s"], L["dw_t"], self.dtype)
+        L["pw2"](rb, dw, resid=x, out=x, out_f32=True)
 
     def run(self, rb, x, final_dtype=None, taps=None, kv_len=None):
         """x: f32 (rows, A) = input-layer output BEFORE the x*sqrt(A) scaling is applied by the caller.

@@ -17,9 +17,9 @@ import torch
 
 from .. import hip
 from ..graphs import GraphCache
-from ..hip import ACT_NONE, ACT_RELU, ACT_TANH
+from ..hip import ACT_NONE, ACT_RELU, ACT_TANH, PackedConv
 from . import _schema as S
-from ._conformer import BN_EPS, LN_EPS, ConformerRunner, PackedConv, SpkProjection
+from ._conformer import BN_EPS, LN_EPS, ConformerRunner, SpkProjection
 from ._prepared import PreparedAcoustic
 
 
@@ -44,9 +44,12 @@ class _Predictor:
     def trunk(self, rb, x_t):
         h = x_t
         for conv, g, b in self.convs:
-            h = hip.conv1d(rb, h, conv.w, conv.c_in, conv.n_out, conv.k, dtype=self.dtype, bias=conv.b, act=ACT_RELU)
-            h = hip.layernorm(h, g, b, self.dtype, LN_EPS)
+            h = hip.layernorm(conv(rb, h, act=ACT_RELU), g, b, self.dtype, LN_EPS)
         return h
+
+    def __call__(self, rb, x_t, want_duration=False):
+        """trunk -> Linear(->1): the prediction per row (want_duration: (log duration, rounded duration))."""
+        return hip.predictor_head(self.trunk(rb, x_t), self.w, self.b, want_duration=want_duration)
 
 
 class FastSpeech2(PreparedAcoustic, torch.nn.Module):
@@ -264,10 +267,9 @@ class FastSpeech2(PreparedAcoustic, torch.nn.Module):
         if self.spk_embed_dim is not None:
             hs = P["proj"](rb, hs, spembs)
         hs_t = hip.affine_cast(hs, dt)
-        p_outs = hip.predictor_head(P["pitch"].trunk(rb, hs_t), P["pitch"].w, P["pitch"].b)
-        e_outs = hip.predictor_head(P["energy"].trunk(rb, hs_t), P["energy"].w, P["energy"].b)
-        logd, d_pred = hip.predictor_head(P["dur"].trunk(rb, hs), P["dur"].w, P["dur"].b,
-                                          want_duration=True)
+        p_outs = P["pitch"](rb, hs_t)
+        e_outs = P["energy"](rb, hs_t)
+        logd, d_pred = P["dur"](rb, hs, want_duration=True)
         hip.variance_embed_add(rb, hs, p_outs, P["pitch_embed"][0], P["pitch_embed"][1],
                                e_outs, P["energy_embed"][0], P["energy_embed"][1])
         if taps is not None:
@@ -289,22 +291,21 @@ class FastSpeech2(PreparedAcoustic, torch.nn.Module):
             P["sqrtA"] = torch.full((A,), math.sqrt(A), dtype=torch.float32, device=dev)
         ys = hip.affine_cast(ys, hip.F32, scale=P["sqrtA"])
         zs_t = P["dec"].run(rbo, ys, final_dtype=dt)                          # T (Rf, A)
-        fo = P["feat_out"]
-        before = hip.conv1d(rbo, zs_t, fo.w, fo.c_in, fo.n_out, 1, dtype=dt, bias=fo.b, out_f32=True)  # (Rf, odim)
-        after = before
-        if P["postnet"]:
-            h = hip.affine_cast(before, dt, ldy=P["postnet"][0].c_in)
-            n = len(P["postnet"])
-            for i, pc in enumerate(P["postnet"]):
-                last = i == n - 1
-                if last:
-                    after = hip.conv1d(rbo, h, pc.w, pc.c_in, pc.n_out, pc.k, dtype=dt, bias=pc.b, act=ACT_NONE,
-                                       resid=before, out_f32=True)
-                else:
-                    h = hip.conv1d(rbo, h, pc.w, pc.c_in, pc.n_out, pc.k, dtype=dt, bias=pc.b, act=ACT_TANH)
+        before, after = self._feat_out(P, rbo, zs_t)
         if taps is not None:
             taps["decoder_out"] = zs_t.float()
-        return after, before
+        return before if after is None else after, before
+
+    @staticmethod
+    def _feat_out(P, rbo, zs_t):
+        """feat_out -> postnet (+ residual).  -> (before (rows, odim) f32, after or None without a postnet)."""
+        before = P["feat_out"](rbo, zs_t, out_f32=True)
+        if not P["postnet"]:
+            return before, None
+        h = hip.affine_cast(before, P["dtype"], ldy=P["postnet"][0].c_in)
+        for pc in P["postnet"][:-1]:
+            h = pc(rbo, h, act=ACT_TANH)
+        return before, P["postnet"][-1](rbo, h, act=ACT_NONE, resid=before, out_f32=True)
 
     def inference(
         self, text: torch.Tensor, feats: Optional[torch.Tensor] = None, durations: Optional[torch.Tensor] = None,
@@ -387,9 +388,9 @@ class FastSpeech2(PreparedAcoustic, torch.nn.Module):
         if self.spk_embed_dim is not None:
             hs = P["proj"](rb, hs, spembs)
         hs_t = hip.affine_cast(hs, dt)
-        p_outs = hip.zero_pad_rows(rb, hip.predictor_head(P["pitch"].trunk(rb, hs_t), P["pitch"].w, P["pitch"].b), kv)
-        e_outs = hip.zero_pad_rows(rb, hip.predictor_head(P["energy"].trunk(rb, hs_t), P["energy"].w, P["energy"].b), kv)
-        d_outs = hip.zero_pad_rows(rb, hip.predictor_head(P["dur"].trunk(rb, hs), P["dur"].w, P["dur"].b), kv)   # log domain
+        p_outs = hip.zero_pad_rows(rb, P["pitch"](rb, hs_t), kv)
+        e_outs = hip.zero_pad_rows(rb, P["energy"](rb, hs_t), kv)
+        d_outs = hip.zero_pad_rows(rb, P["dur"](rb, hs), kv)   # log domain
         # ground-truth pitch / energy embeddings (:618-622), then the length regulator on the ground-truth durations
         hip.variance_embed_add(rb, hs, ps.reshape(-1).contiguous(), P["pitch_embed"][0], P["pitch_embed"][1],
                                es.reshape(-1).contiguous(), P["energy_embed"][0], P["energy_embed"][1])
@@ -409,18 +410,7 @@ class FastSpeech2(PreparedAcoustic, torch.nn.Module):
         yl = hip.affine_cast(yl, hip.F32, scale=P["sqrtA"])
         kvo = olens.to(device=dev, dtype=torch.int32).contiguous()  # h_masks = _source_mask(olens) (:636-637)
         zs_t = P["dec"].run(rbo, yl, final_dtype=dt, kv_len=kvo)
-        fo = P["feat_out"]
-        before = hip.conv1d(rbo, zs_t, fo.w, fo.c_in, fo.n_out, 1, dtype=dt, bias=fo.b, out_f32=True)
-        after = None
-        if P["postnet"]:
-            h = hip.affine_cast(before, dt, ldy=P["postnet"][0].c_in)
-            n = len(P["postnet"])
-            for i, pc in enumerate(P["postnet"]):
-                if i == n - 1:
-                    after = hip.conv1d(rbo, h, pc.w, pc.c_in, pc.n_out, pc.k, dtype=dt, bias=pc.b, act=ACT_NONE,
-                                       resid=before, out_f32=True)
-                else:
-                    h = hip.conv1d(rbo, h, pc.w, pc.c_in, pc.n_out, pc.k, dtype=dt, bias=pc.b, act=ACT_TANH)
+        before, after = self._feat_out(P, rbo, zs_t)
         od = self.odim
         return {
             "before_outs": before.view(B, To, od),

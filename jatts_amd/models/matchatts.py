@@ -20,9 +20,9 @@ from typing import Optional, Sequence
 import torch
 
 from .. import hip
-from ..hip import ACT_MISH, ACT_NONE, ACT_RELU, ACT_SWISH
+from ..hip import ACT_MISH, ACT_NONE, ACT_RELU, ACT_SWISH, PackedConv
 from . import _schema as S
-from ._conformer import ConformerRunner, PackedConv, SpkProjection
+from ._conformer import ConformerRunner, SpkProjection
 from ._prepared import PreparedAcoustic
 from .fastspeech2 import _Predictor
 
@@ -63,23 +63,22 @@ class _Resnet:
         C = self.c_out
         h = None
         for x, cv in zip(xs, self.conv1):
-            h = hip.conv1d(rb, x, cv.w, cv.c_in, C, 3, dtype=dt, bias=cv.b, resid=h, out=h, out_f32=True,
-                           ldx=x.shape[1])
+            h = cv(rb, x, resid=h, out=h, out_f32=True, ldx=x.shape[1])
         # the time vector depends only on (Euler step, n_timesteps, batch size): cached across batches by the caller
         tv = tv_cache.get(id(self)) if tv_cache is not None else None
         if tv is None:
-            tv = hip.conv1d(rbs, tmish, self.mlp.w, self.mlp.c_in, C, 1, dtype=dt, bias=self.mlp.b, out_f32=True)
+            tv = self.mlp(rbs, tmish, out_f32=True)
             if tv_cache is not None:
                 tv_cache[id(self)] = tv
         h = hip.groupnorm_mish(rb, h, C, 8, self.gn1[0], self.gn1[1], dt, GN_EPS, addvec=tv)
         if valid is not None:
             hip.zero_pad_rows(rb, h, valid)          # block1(x) * mask, + time vector, then block2's own x * mask
-        h = hip.conv1d(rb, h, self.conv2.w, self.conv2.c_in, C, 3, dtype=dt, bias=self.conv2.b)
+        h = self.conv2(rb, h)
         out = hip.groupnorm_mish(rb, h, C, 8, self.gn2[0], self.gn2[1], hip.F32, GN_EPS)
         if valid is not None:
             hip.zero_pad_rows(rb, out, valid)        # block2 output * mask; res_conv(x * mask) below adds its bias at padded rows
         for x, cv in zip(xs, self.res):
-            hip.conv1d(rb, x, cv.w, cv.c_in, C, 1, dtype=dt, bias=cv.b, resid=out, out=out, out_f32=True, ldx=x.shape[1])
+            cv(rb, x, resid=out, out=out, out_f32=True, ldx=x.shape[1])
         return out
 
 
@@ -115,21 +114,21 @@ class _TBlock:
     def run(self, rb, x, dt, key_bias=None):
         """x: f32 (rows, C), updated in place.  key_bias f32 (rows, heads) or None: added to every score of that key AFTER the
         1/sqrt(d) scaling -- diffusers adds `attention_mask` to the scores [recalled]; Matcha passes its 1/0 frame mask."""
-        C, I = x.shape[1], self.inner
+        I = self.inner
         n = hip.layernorm(x, self.n1[0], self.n1[1], dt, GN_EPS)
         vcol, ldvt = rb.vt_layout()
         if self.qkv is not None:
-            qk, vt = hip.conv1d(rb, n, self.qkv.w, self.qkv.c_in, 3 * I, 1, dtype=dt, split=(2 * I, ldvt, vcol))
+            qk, vt = self.qkv(rb, n, split=(2 * I, ldvt, vcol))
         else:
-            qk = hip.conv1d(rb, n, self.qk.w, self.qk.c_in, 2 * I, 1, dtype=dt)
-            vt = hip.conv1d(rb, n, self.v.w, self.v.c_in, I, 1, dtype=dt, transposed=True, out_ld=ldvt, y_seq_col0=vcol)
+            qk = self.qk(rb, n)
+            vt = self.v(rb, n, transposed=True, out_ld=ldvt, y_seq_col0=vcol)
         a = hip.relpos_attention(rb, qk, 2 * I, qk, 2 * I, vt, ldvt, None, 0, key_bias, self.dh ** -0.5, self.heads,
                                  self.dh, hip.attention_dtype(dt, self.split, self.attn, self.heads, self.dh, 0), q_col0=0, k_col0=I, rel_mode=0, vt_col0=vcol)
-        hip.conv1d(rb, a, self.o.w, self.o.c_in, C, 1, dtype=dt, bias=self.o.b, resid=x, out=x, out_f32=True)
+        self.o(rb, a, resid=x, out=x, out_f32=True)
         n = hip.layernorm(x, self.n3[0], self.n3[1], dt, GN_EPS)
         # SnakeBeta rides in the epilogue of the conv that feeds it (one launch and one round trip of the widest tensor less)
-        u = hip.conv1d(rb, n, self.ff1.w, self.ff1.c_in, self.ff1.n_out, 1, dtype=dt, bias=self.ff1.b, snake=(self.alpha, self.inv_beta))
-        hip.conv1d(rb, u, self.ff2.w, self.ff2.c_in, C, 1, dtype=dt, bias=self.ff2.b, resid=x, out=x, out_f32=True)
+        u = self.ff1(rb, n, snake=(self.alpha, self.inv_beta))
+        self.ff2(rb, u, resid=x, out=x, out_f32=True)
 
 
 class _MatchaBase(PreparedAcoustic, torch.nn.Module):
@@ -304,7 +303,6 @@ class _MatchaBase(PreparedAcoustic, torch.nn.Module):
         (valid = (int32 lengths at full rate, at half rate, key-bias rows at full rate, at half rate)): PADDED batch with the
         reference's mask multiplications (decoder.py:413-487); returns v(x) * mask as f32 and leaves x32 alone."""
         dt = P["dtype"]
-        od = self.odim
         ld_in = P["d0"][0].conv1[0].c_in
         x_t = hip.affine_cast(x32, dt, ldy=ld_in)
         v1 = v2 = kb1 = kb2 = None
@@ -316,8 +314,7 @@ class _MatchaBase(PreparedAcoustic, torch.nn.Module):
         tcache = P.setdefault("tcache", {}).setdefault(tkey, {}) if tkey is not None else None
         tm = tcache.get("tm") if tcache is not None else None
         if tm is None:
-            t1 = hip.conv1d(rbs, temb_rows, P["t1"].w, P["t1"].c_in, P["t1"].n_out, 1, dtype=dt, bias=P["t1"].b, act=ACT_SWISH)
-            tm = hip.conv1d(rbs, t1, P["t2"].w, P["t2"].c_in, P["t2"].n_out, 1, dtype=dt, bias=P["t2"].b, act=ACT_MISH)
+            tm = P["t2"](rbs, P["t1"](rbs, temb_rows, act=ACT_SWISH), act=ACT_MISH)
             if tcache is not None:
                 tcache["tm"] = tm
 
@@ -339,30 +336,27 @@ class _MatchaBase(PreparedAcoustic, torch.nn.Module):
         h0 = stage(P["d0"], rb, [x_t, mu_t], v1, kb1)            # (R, C0) f32; skip connection 0
         h0_t = masked(rb, operand(h0), v1)
         C0 = h0.shape[1]
-        dn = P["down"]
-        h = hip.conv1d(rb2, h0_t.view(-1, 2 * C0), dn.w, dn.c_in, C0, 2, dtype=dt, bias=dn.b, pad=1)   # (R/2, C0)
+        h = P["down"](rb2, h0_t.view(-1, 2 * C0), pad=1)            # (R/2, C0)
         h1 = stage(P["d1"], rb2, [masked(rb2, h, v2)], v2, kb2)  # skip connection 1
         h1_t = masked(rb2, operand(h1), v2)
-        c = P["d1c"]
-        h = hip.conv1d(rb2, h1_t, c.w, c.c_in, c.n_out, 3, dtype=dt, bias=c.b)
+        h = P["d1c"](rb2, h1_t)
         for blk in P["mid"]:
             h = operand(stage(blk, rb2, [masked(rb2, h, v2)], v2, kb2))
         h = stage(P["u0"], rb2, [masked(rb2, h, v2), h1_t], v2, kb2)
         up, pad = P["up"]
         C1 = h.shape[1]
-        h = hip.conv1d(rb2, masked(rb2, operand(h), v2), up.w, up.c_in, 2 * C1, up.k, dtype=dt, bias=up.b, pad=pad)
+        h = up(rb2, masked(rb2, operand(h), v2), pad=pad)         # (R/2, 2 C1)
         h = h.view(-1, C1)                                        # (R, C1): polyphase rows are already interleaved
         h = stage(P["u1"], rb, [masked(rb, h, v1), h0_t], v1, kb1)
-        c = P["u1c"]
-        h = hip.conv1d(rb, masked(rb, operand(h), v1), c.w, c.c_in, c.n_out, 3, dtype=dt, bias=c.b)
+        h = P["u1c"](rb, masked(rb, operand(h), v1))
         fbc, g, b = P["fb"]
-        h = hip.conv1d(rb, masked(rb, h, v1), fbc.w, fbc.c_in, fbc.n_out, 3, dtype=dt, bias=fbc.b)
+        h = fbc(rb, masked(rb, h, v1))
         h = masked(rb, hip.groupnorm_mish(rb, h, fbc.n_out, 8, g, b, dt, GN_EPS), v1)
         fp = P["fp"]
         if valid is not None:   # the vector field itself, masked (decoder.py:485-487)
-            return masked(rb, hip.conv1d(rb, h, fp.w, fp.c_in, od, 1, dtype=dt, bias=fp.b, out_f32=True), v1)
+            return masked(rb, fp(rb, h, out_f32=True), v1)
         # Euler update fused into the projection epilogue: x += dt * (W h + b)   (flow_matching.py:86-88)
-        hip.conv1d(rb, h, fp.w, fp.c_in, od, 1, dtype=dt, bias=fp.b, alpha=dt_step, resid=x32, out=x32, out_f32=True)
+        fp(rb, h, alpha=dt_step, resid=x32, out=x32, out_f32=True)
 
     @torch.no_grad()
     def inference_batch(self, texts, n_timesteps: int = 10, temperature: float = 0.667, spembs=None, sids=None,
@@ -382,8 +376,7 @@ class _MatchaBase(PreparedAcoustic, torch.nn.Module):
             hs = P["proj"](rb, hs, spembs)
         if taps is not None:
             taps["hs"] = hs.clone()                                 # text encoding (+ speaker): what the alignment module scores
-        logd, d_pred = hip.predictor_head(P["dur"].trunk(rb, hs), P["dur"].w, P["dur"].b,
-                                          want_duration=True)
+        logd, d_pred = P["dur"](rb, hs, want_duration=True)
         d_used = d_pred
         if durations is not None:
             d_used = torch.cat([d.reshape(-1) for d in durations]).to(device=dev, dtype=torch.int64).contiguous()
@@ -396,8 +389,7 @@ class _MatchaBase(PreparedAcoustic, torch.nn.Module):
             up = hip.gaussian_upsample(rb, d_eff, rbo, hs)
         else:           # MatchaTTS (tts1): hard LengthRegulator (matchatts.py:427)
             up = hip.lr_gather(rb, cum, rbo, hs)
-        ep = P["eproj"]
-        mu = hip.conv1d(rbo, hip.affine_cast(up, dt), ep.w, ep.c_in, od, 1, dtype=dt, bias=ep.b, out_f32=True)
+        mu = P["eproj"](rbo, hip.affine_cast(up, dt), out_f32=True)
         if taps is not None:
             taps["mu"] = mu.clone()
         if noise is None:
@@ -499,7 +491,7 @@ class _MatchaBase(PreparedAcoustic, torch.nn.Module):
             rbv = hip.RaggedBatch(ilens, dev)                          # valid tokens, packed (row selection: plumbing)
             sel = torch.cat([torch.arange(b * Tm, b * Tm + ilens[b], device=dev) for b in range(B)])
             # ---- duration predictor (log domain, masked) and masked Gaussian upsampling
-            d_outs = hip.zero_pad_rows(rbt, hip.predictor_head(P["dur"].trunk(rbt, hs), P["dur"].w, P["dur"].b), kv).view(B, Tm)
+            d_outs = hip.zero_pad_rows(rbt, P["dur"](rbt, hs), kv).view(B, Tm)
             d_int = torch.cat([ds[b, : ilens[b]] for b in range(B)]).to(torch.int64).contiguous()
             rbo = hip.RaggedBatch(olens, dev)
             up = hip.gaussian_upsample(rbv, d_int, rbo, hs.index_select(0, sel).contiguous())    # valid frames of every utterance
@@ -510,17 +502,15 @@ class _MatchaBase(PreparedAcoustic, torch.nn.Module):
         else:   # tts1: ground-truth durations, hard length regulator, zero padding (length_regulator.py:70-97)
             if durations is None:
                 raise ValueError("MatchaTTS.forward needs durations")
-            d_outs = hip.zero_pad_rows(rbt, hip.predictor_head(P["dur"].trunk(rbt, hs), P["dur"].w, P["dur"].b), kv).view(B, Tm)
+            d_outs = hip.zero_pad_rows(rbt, P["dur"](rbt, hs), kv).view(B, Tm)
             d_flat = durations[:, : int(durations_lengths.max())].to(dev).reshape(-1).to(torch.int64).contiguous()
             if d_flat.numel() != B * Tm:
                 raise ValueError("durations must be padded to the text length")
             _, cum, _, _ = hip.lr_durations(rbt, d_flat, 1.0, zero_rule=0)
             up_pad = hip.lr_gather(rbt, cum, hip.RaggedBatch([Te] * B, dev), hs)
             ds = log_p_attn = bin_loss = None
-        ep = P["eproj"]
         rbe = hip.RaggedBatch([Te] * B, dev)
-        mu = hip.conv1d(rbe, hip.affine_cast(up_pad, dt), ep.w, ep.c_in, od, 1, dtype=dt, bias=ep.b,
-                        out_f32=True)                              # hs of the return dict: (B, Te, odim)
+        mu = P["eproj"](rbe, hip.affine_cast(up_pad, dt), out_f32=True)   # hs of the return dict: (B, Te, odim)
         ys_e = ys[:, :Te].contiguous()
         # ---- CFM loss (flow_matching.py:99-127)
         t = (torch.rand(B) if cfm_t is None else cfm_t.reshape(B).float().cpu())

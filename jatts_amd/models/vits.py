@@ -16,8 +16,9 @@ from typing import Optional, Sequence
 import torch
 
 from .. import hip
+from ..hip import PackedConv
 from . import _schema as S
-from ._conformer import LN_EPS, ConformerRunner, PackedConv, SpkProjection
+from ._conformer import ConformerRunner, SpkProjection
 from ._prepared import PreparedAcoustic
 from .fastspeech2 import _Predictor
 
@@ -177,15 +178,27 @@ class VITS(PreparedAcoustic, torch.nn.Module):
         dt, A = P["dtype"], self.adim
         skips = torch.zeros_like(h)
         for ly in layers:
-            g = hip.conv1d(rbs, sp_t, ly["glo"].w, ly["glo"].c_in, 2 * A, 1, dtype=dt, out_f32=True)  # (B, 2A)
-            cv = ly["conv"]
-            y = hip.conv1d(rbo, hip.affine_cast(h, dt), cv.w, cv.c_in, 2 * A, cv.k, dtype=dt, bias=cv.b)
+            g = ly["glo"](rbs, sp_t, out_f32=True)                                            # (B, 2A)
+            y = ly["conv"](rbo, hip.affine_cast(h, dt))
             gate = hip.gated_tanh_sigmoid(rbo, y, g, A, dt)
-            hip.conv1d(rbo, gate, ly["skip"].w, ly["skip"].c_in, A, 1, dtype=dt, bias=ly["skip"].b, resid=skips,
-                       out=skips, out_f32=True)
-            hip.conv1d(rbo, gate, ly["res"].w, ly["res"].c_in, A, 1, dtype=dt, bias=ly["res"].b, resid=h, out=h,
-                       out_f32=True)
+            ly["skip"](rbo, gate, resid=skips, out=skips, out_f32=True)
+            ly["res"](rbo, gate, resid=h, out=h, out_f32=True)
         return skips
+
+    def _coupling(self, P, rbo, rbs, z, fl, sp_t, alpha):
+        """One coupling step of the flow on z f32 (rows, A), in place: xb <- xb + alpha * proj(wavenet(inp(xa)) * sqrt(1 / layers))
+        (use_only_mean: logs = 0); alpha = 1 forward, -1 inverse.  The FlipFlow around it is the caller's."""
+        dt, A = P["dtype"], self.adim
+        h = fl["inp"](rbo, hip.affine_cast(z, dt), out_f32=True, ldx=A)    # reads the first half only: (rows, A) f32
+        sk = self._wavenet(P, rbo, rbs, h, fl["layers"], sp_t)
+        scale = P.setdefault("skip_scale", torch.full((A,), math.sqrt(1.0 / len(fl["layers"])), device=P["dev"]))
+        fl["proj"](rbo, hip.affine_cast(sk, dt, scale=scale), alpha=alpha, resid=z, resid_col0=A // 2, out=z, out_ld=A, out_col0=A // 2,
+                   out_f32=True)
+
+    def _decode(self, P, rb, z, kv_len=None):
+        """z f32 (rows, A) -> decoder (x * sqrt(A) first) -> feat_out: f32 (rows, odim)."""
+        zs_t = P["dec"].run(rb, hip.affine_cast(z, hip.F32, scale=P["sqrtA"]), final_dtype=P["dtype"], kv_len=kv_len)
+        return P["feat_out"](rb, zs_t, out_f32=True)
 
     def _post(self, P):
         """Posterior encoder + alignment convolutions: prepared on first use (training-time forward(), inference(feats=...))."""
@@ -205,11 +218,10 @@ class VITS(PreparedAcoustic, torch.nn.Module):
         """PosteriorEncoder.forward on ragged valid frames (posterior_encoder.py:96-130): -> (z, stats_q = m_q | logs_q)."""
         dt, A, post = P["dtype"], self.adim, self._post(P)
         q = post["inp"]
-        h = hip.conv1d(rbo, hip.affine_cast(yv, dt, ldy=q.c_in), q.w, q.c_in, A, 1, dtype=dt, bias=q.b, out_f32=True)
+        h = q(rbo, hip.affine_cast(yv, dt, ldy=q.c_in), out_f32=True)
         sk = self._wavenet(P, rbo, rbs, h, post["layers"], sp_t)
         scale_q = torch.full((A,), math.sqrt(1.0 / len(post["layers"])), device=P["dev"])
-        pp = post["proj"]
-        stats_q = hip.conv1d(rbo, hip.affine_cast(sk, dt, scale=scale_q), pp.w, pp.c_in, 2 * A, 1, dtype=dt, bias=pp.b, out_f32=True)
+        stats_q = post["proj"](rbo, hip.affine_cast(sk, dt, scale=scale_q), out_f32=True)
         return hip.gaussian_sample(stats_q, noise_rows, 1.0), stats_q                    # z = m_q + eps * exp(logs_q)
 
     def _wn_layers(self, sd, prefix, n_layers, dt, dev):
@@ -240,16 +252,14 @@ class VITS(PreparedAcoustic, torch.nn.Module):
         if taps is not None:
             taps["text_encoder_out"] = hs.clone()
         hs_t = hip.affine_cast(hs, dt)
-        tp = P["te_proj"]
-        stats = hip.conv1d(rb, hs_t, tp.w, tp.c_in, 2 * A, 1, dtype=dt, bias=tp.b, out_f32=True)   # (R, 2A): m_p | logs_p
+        stats = P["te_proj"](rb, hs_t, out_f32=True)                       # (R, 2A): m_p | logs_p
         # speaker embedding: hs += projection(normalize(spembs))  (vits.py:441-443, :706-712)
         spembs = spembs.to(dev).float().reshape(B, -1).contiguous()
         rbs = hip.RaggedBatch([1] * B, dev)
         hs = P["proj"](rb, hs, spembs)
         if taps is not None:
             taps["hs"] = hs.clone()                                        # text encoding + speaker: what the alignment module scores
-        logd, d_pred = hip.predictor_head(P["dur"].trunk(rb, hs), P["dur"].w, P["dur"].b,
-                                          want_duration=True)
+        logd, d_pred = P["dur"](rb, hs, want_duration=True)
         d_used = d_pred
         if durations is not None:
             d_used = torch.cat([d.reshape(-1) for d in durations]).to(device=dev, dtype=torch.int64).contiguous()
@@ -268,25 +278,12 @@ class VITS(PreparedAcoustic, torch.nn.Module):
             taps["z_p"] = z.clone()
         # global conditioning vectors g = conv1x1_glo(spembs) per flow layer (residual_block.py:150-154)
         sp_t = hip.affine_cast(spembs, dt, ldy=P["flows"][0]["layers"][0]["glo"].c_in)
-        half = A // 2
         for fl in reversed(P["flows"]):
-            z = hip.flip_channels(z)                                      # FlipFlow
-            xa_t = hip.affine_cast(z, dt)                                  # coupling reads the first half only
-            fi = fl["inp"]
-            h = hip.conv1d(rbo, xa_t, fi.w, fi.c_in, A, 1, dtype=dt, bias=fi.b, out_f32=True, ldx=A)  # (Rf, A) f32
-            skips = self._wavenet(P, rbo, rbs, h, fl["layers"], sp_t)
-            # m = proj(skips * sqrt(1/layers));  xb <- xb - m   (use_only_mean: logs = 0)
-            sk_t = hip.affine_cast(skips, dt, scale=P.setdefault(
-                "skip_scale", torch.full((A,), math.sqrt(1.0 / len(fl["layers"])), device=dev)))
-            pr = fl["proj"]
-            hip.conv1d(rbo, sk_t, pr.w, pr.c_in, half, 1, dtype=dt, bias=pr.b, alpha=-1.0, resid=z, resid_col0=half,
-                       out=z, out_ld=A, out_col0=half, out_f32=True)
+            z = hip.flip_channels(z)                                      # FlipFlow, then the inverse coupling (xb <- xb - m)
+            self._coupling(P, rbo, rbs, z, fl, sp_t, -1.0)
         if taps is not None:
             taps["z"] = z.clone()
-        zs_t = P["dec"].run(rbo, hip.affine_cast(z, hip.F32, scale=P["sqrtA"]), final_dtype=dt)
-        fo = P["feat_out"]
-        out = hip.conv1d(rbo, zs_t, fo.w, fo.c_in, fo.n_out, 1, dtype=dt, bias=fo.b, out_f32=True)
-        return dict(feat_gen=out, olens=olens, feats_rb=rbo, text_rb=rb, duration=d_pred, log_duration=logd)
+        return dict(feat_gen=self._decode(P, rbo, z), olens=olens, feats_rb=rbo, text_rb=rb, duration=d_pred, log_duration=logd)
 
     def inference(self, text, feats=None, durations=None, spembs=None, sids=None, lids=None, n_timesteps=None,
                   temperature=None, noise_scale: float = 0.667, use_teacher_forcing: bool = False, noise=None, post_noise=None):
@@ -314,10 +311,7 @@ class VITS(PreparedAcoustic, torch.nn.Module):
             sp_t = hip.affine_cast(sp, dt, ldy=P["flows"][0]["layers"][0]["glo"].c_in)
             nz = (torch.randn(Tf, A) if post_noise is None else post_noise.float()).to(dev).contiguous()
             z_bar, _ = self._posterior(P, rbo, rbs, ys[0], sp_t, nz)
-            zs = P["dec"].run(rbo, hip.affine_cast(z_bar, hip.F32, scale=P["sqrtA"]), final_dtype=dt)
-            fo = P["feat_out"]
-            out.update(log_p_attn=lp[0], ds=ds[0],
-                       outs_bar=hip.conv1d(rbo, zs, fo.w, fo.c_in, fo.n_out, 1, dtype=dt, bias=fo.b, out_f32=True))
+            out.update(log_p_attn=lp[0], ds=ds[0], outs_bar=self._decode(P, rbo, z_bar))
         return out
 
     def forward(self, text, text_lengths, feats, feats_lengths, durations=None, durations_lengths=None, spembs=None, sids=None,
@@ -351,9 +345,7 @@ class VITS(PreparedAcoustic, torch.nn.Module):
         kv = hip.h2d(ilens, torch.int32, dev)
         # ---- text encoder on the padded batch (text_encoder.py:104-140)
         hs = P["tenc"].run(rbt, hip.embed_scale(xs.reshape(-1).to(torch.int64).contiguous(), P["emb"], float(A)), kv_len=kv)
-        tp = P["te_proj"]
-        stats_p = hip.zero_pad_rows(rbt, hip.conv1d(rbt, hip.affine_cast(hs, dt), tp.w, tp.c_in, 2 * A, 1, dtype=dt, bias=tp.b,
-                                                    out_f32=True), kv)                 # proj(x) * x_mask: m_p | logs_p
+        stats_p = hip.zero_pad_rows(rbt, P["te_proj"](rbt, hip.affine_cast(hs, dt), out_f32=True), kv)   # proj(x) * x_mask: m_p | logs_p
         spembs = spembs.to(dev).float().reshape(B, -1).contiguous()
         hs = P["proj"](rbt, hs, spembs)
         # ---- posterior encoder + forward flow on the valid frames (ragged)
@@ -364,23 +356,16 @@ class VITS(PreparedAcoustic, torch.nn.Module):
         sp_t = hip.affine_cast(spembs, dt, ldy=P["flows"][0]["layers"][0]["glo"].c_in)               # g = spembs, unnormalised
         nz = (torch.randn(B, To, A) if post_noise is None else post_noise[:, :To].float()).to(dev).reshape(B * To, A)
         z, stats_q = self._posterior(P, rbo, rbs, yv, sp_t, nz.index_select(0, fsel).contiguous())
-        half = A // 2
         zp = z.clone()
-        skip_scale = P.setdefault("skip_scale", torch.full((A,), math.sqrt(1.0 / self.flow_layers), device=dev))
         for fl in P["flows"]:                                              # coupling (xb <- m + xb), then FlipFlow
-            fi = fl["inp"]
-            h = hip.conv1d(rbo, hip.affine_cast(zp, dt), fi.w, fi.c_in, A, 1, dtype=dt, bias=fi.b, out_f32=True, ldx=A)
-            sk = self._wavenet(P, rbo, rbs, h, fl["layers"], sp_t)
-            pr = fl["proj"]
-            hip.conv1d(rbo, hip.affine_cast(sk, dt, scale=skip_scale), pr.w, pr.c_in, half, 1, dtype=dt, bias=pr.b, alpha=1.0,
-                       resid=zp, resid_col0=half, out=zp, out_ld=A, out_col0=half, out_f32=True)
+            self._coupling(P, rbo, rbs, zp, fl, sp_t, 1.0)
             zp = hip.flip_channels(zp)
         # ---- alignment module on the padded batch + monotonic alignment search (jatts_amd.alignments.padded_alignment)
         from ..alignments import padded_alignment
         log_p_attn, ds, bin_loss = padded_alignment(P["align"], hs, ys, ilens, olens, A)
         rbf, rbv = hip.RaggedBatch([To] * B, dev), hip.RaggedBatch(ilens, dev)
         tsel = torch.cat([torch.arange(b * Tm, b * Tm + ilens[b], device=dev) for b in range(B)])
-        d_outs = hip.zero_pad_rows(rbt, hip.predictor_head(P["dur"].trunk(rbt, hs), P["dur"].w, P["dur"].b), kv).view(B, Tm)
+        d_outs = hip.zero_pad_rows(rbt, P["dur"](rbt, hs), kv).view(B, Tm)
         # ---- prior statistics upsampled with the MAS durations (padded frames take the value of frame 0, length_regulator.py:139-141)
         d_int = torch.cat([ds[b, : ilens[b]] for b in range(B)]).to(torch.int64).contiguous()
         up = hip.gaussian_upsample(rbv, d_int, rbo, stats_p.index_select(0, tsel).contiguous())      # (valid frames, 2A)
@@ -394,9 +379,7 @@ class VITS(PreparedAcoustic, torch.nn.Module):
             return out.view(B, To, -1)
         z_pad = pad_frames(z)
         kvo = hip.h2d(olens, torch.int32, dev)
-        zs_t = P["dec"].run(rbf, hip.affine_cast(z_pad.view(B * To, A), hip.F32, scale=P["sqrtA"]), final_dtype=dt, kv_len=kvo)
-        fo = P["feat_out"]
-        outs = hip.conv1d(rbf, zs_t, fo.w, fo.c_in, fo.n_out, 1, dtype=dt, bias=fo.b, out_f32=True).view(B, To, od)
+        outs = self._decode(P, rbf, z_pad.view(B * To, A), kv_len=kvo).view(B, To, od)
         sq = pad_frames(stats_q)
         y_mask = (torch.arange(To, device=dev).unsqueeze(0) < kvo.unsqueeze(1)).float().unsqueeze(1)
         tr = lambda v: v.transpose(1, 2)   # noqa: E731  the reference keeps these channel-first

@@ -21,9 +21,9 @@ import torch
 from . import hip
 from .features.common import PackedWaves, require_cuda
 from .wavio import decode_wav
-from .hip import ACT_NONE, ACT_RELU, ACT_TANH
+from .hip import ACT_NONE, ACT_RELU, ACT_TANH, PackedConv
 from .models import _schema as S
-from .models._conformer import BN_EPS, PackedConv
+from .models._conformer import BN_EPS
 
 F32 = hip.F32
 
@@ -113,8 +113,7 @@ class ECAPA_TDNN(torch.nn.Module):
     def _tdnn(self, rb, x, t, dil=1, x_col0=0, ldx=None, xs=None, out=None, out_col0=0, ldy=None):
         """TDNNBlock: conv ("same", reflect) -> ReLU -> BatchNorm(eval), f32 in / out."""
         pc, s, sh = t
-        h = hip.conv1d(rb, xs if xs is not None else x, pc.w, pc.c_in, pc.n_out, pc.k, dtype=F32, dil=dil, bias=pc.b, act=ACT_RELU,
-                       reflect=pc.k > 1, x_col0=x_col0, ldx=ldx)
+        h = pc(rb, xs if xs is not None else x, dil=dil, act=ACT_RELU, reflect=pc.k > 1, x_col0=x_col0, ldx=ldx)
         return hip.affine_cast(h, F32, scale=s, shift=sh, ldy=ldy, out=out, out_col0=out_col0)
 
     @torch.no_grad()
@@ -140,22 +139,21 @@ class ECAPA_TDNN(torch.nn.Module):
                                out=y, out_col0=j * G)
             h = self._tdnn(rb, y, B["t2"])
             s = hip.seq_mean_std(rb, h, C, want_std=False)                                       # squeeze: mean over time
-            s = hip.conv1d(rbs, s, B["se1"].w, B["se1"].c_in, B["se1"].n_out, 1, dtype=F32, bias=B["se1"].b, act=ACT_RELU)
-            s = hip.conv1d(rbs, s, B["se2"].w, B["se2"].c_in, B["se2"].n_out, 1, dtype=F32, bias=B["se2"].b)
+            s = B["se2"](rbs, B["se1"](rbs, s, act=ACT_RELU))
             hip.se_scale_add(rb, h, s, resid=x, out=cat, out_col0=(i - 1) * C)                   # gate + residual -> concat slot
             x = torch.empty(rb.total, C, dtype=torch.float32, device=feats.device)
             hip.affine_cast(cat, F32, x_col0=(i - 1) * C, dim=C, out=x)                          # next block's input (contiguous)
         m = self._tdnn(rb, cat, P["mfa"], self.dilations[4])                                     # (rows, M)
         # attentive statistics pooling with global context: W [x; mean; std] = W_x x + (W_g [mean; std]) per utterance
         g = hip.seq_mean_std(rb, m, M)                                                           # (B, 2M)
-        gv = hip.conv1d(rbs, g, P["asp_g"].w, P["asp_g"].c_in, self.att, 1, dtype=F32)
-        a = hip.conv1d(rb, m, P["asp_x"].w, P["asp_x"].c_in, self.att, 1, dtype=F32, bias=P["asp_x"].b)
+        gv = P["asp_g"](rbs, g)
+        a = P["asp_x"](rb, m)
         a = hip.seq_affine_act(rb, a, self.att, F32, seq_vec=gv, pre_act=ACT_RELU, scale=P["asp_bn"][0], shift=P["asp_bn"][1],
                                post_act=ACT_TANH, ldy=P["asp_conv"].c_in)
-        logits = hip.conv1d(rb, a, P["asp_conv"].w, P["asp_conv"].c_in, M, 1, dtype=F32, bias=P["asp_conv"].b)
+        logits = P["asp_conv"](rb, a)
         pooled = hip.seq_mean_std(rb, m, M, logits=logits)                                       # (B, 2M) attention-weighted
         pooled = hip.affine_cast(pooled, F32, scale=P["pool_bn"][0], shift=P["pool_bn"][1])
-        return hip.conv1d(rbs, pooled, P["fc"].w, P["fc"].c_in, self.lin_neurons, 1, dtype=F32, bias=P["fc"].b)
+        return P["fc"](rbs, pooled)
 
 
 class FbankFrontEnd:
@@ -197,9 +195,9 @@ class FbankFrontEnd:
         pw = PackedWaves.from_list(waves, self.window.device)
         rb = hip.RaggedBatch([1 + n // self.hop for n in pw.lens], pw.x.device)
         frames = hip.frame_signal(rb, pw.cu, pw.x, self.window, self.n_fft, self.hop, self.ldf)
-        spec = hip.conv1d(rb, frames, self.dft.w, self.dft.c_in, 2 * self.nbp, 1, dtype=F32)            # [re | im]
+        spec = self.dft(rb, frames)                                # [re | im]
         power = hip.power_spectrum(spec, self.nbp, self.ldp)
-        mel = hip.conv1d(rb, power, self.mel.w, self.mel.c_in, self.n_mels, 1, dtype=F32)
+        mel = self.mel(rb, power)
         return rb, hip.fbank_post(rb, mel, self.n_mels, self.ldo)
 
 

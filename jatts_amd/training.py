@@ -17,7 +17,6 @@ import torch
 import torch.distributed as dist
 
 from . import graphs, hip
-from .models._conformer import PackedConv
 
 L1, L2 = 0, 1
 

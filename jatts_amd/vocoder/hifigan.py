@@ -18,7 +18,7 @@ import torch
 
 from .. import hip
 from ..graphs import GraphCache
-from ..models._conformer import PackedConv
+from ..hip import PackedConv
 from ..models._prepared import Prepared
 from ..models import _schema as S
 from ..precision import TABLE
@@ -248,15 +248,14 @@ class HiFiGANGenerator(Prepared, torch.nn.Module):
         dt, udt = P["dtype"], P["unit_dtype"]
         pin = P["in"]
         x = hip.affine_cast(mel, dt, scale=scale, shift=shift, ldy=pin.c_in)
-        x = hip.conv1d(rb, x, pin.w, pin.c_in, pin.n_out, pin.k, dtype=dt, bias=pin.b)
+        x = pin(rb, x)
         if taps is not None:
             taps["input_conv"] = x.float()
         xs, in_scale, rate = [x], 1.0, 1
         supported = P["unit_channels"]
         for i, (pc, pad, s, c_out, win) in enumerate(P["ups"]):
             rows = rb.total * rate
-            up = hip.conv1d(rb, xs, pc.w, pc.c_in, pc.n_out, pc.k, dtype=dt, bias=pc.b, pad=pad,
-                            pre_lrelu=self.slope, in_scale=in_scale, len_mul=rate, tap_window=win)       # (rows, s*c_out)
+            up = pc(rb, xs, pad=pad, pre_lrelu=self.slope, in_scale=in_scale, len_mul=rate, tap_window=win)       # (rows, s*c_out)
             rate *= s
             up = up.view(rows * s, c_out)
             if taps is not None:
