@@ -2,7 +2,7 @@
 # egs/jsut/tts2 on the MI355X path: the reference recipe's interface (same variables, same --option syntax, same directory
 # layout: exp/<expname>/{config.yml,stats.h5,tokens.txt,*.pkl} -> exp/<expname>/results/<checkpoint>/<set>/wav/*.wav) with
 # stage 1 (feature extraction and statistics, egs/common/stage1.sh), stages 2 and 3 (token list and training, egs/common/stage3.sh) and stage 4
-# (network decoding, egs/common/stage4.sh) running on jatts_amd.  Stages -1, 0 (download, data preparation) and 5 (evaluation) are the reference's
+# (network decoding, egs/common/stage4.sh) and stage 5 (objective evaluation, egs/common/stage5.sh) running on jatts_amd.  Stages -1, 0 (download, data preparation) are the reference's
 # and are not rebuilt here: run them there, or start this script inside the reference's recipe directory.
 #     ./run.sh --stage 2 --stop_stage 3 [--conf conf/fastspeech2.v1.yaml] [--tag mytag] [--resume exp/.../checkpoint-10000steps.pkl] [--n_gpus 8]
 #     ./run.sh --stage 1 --stop_stage 1 [--conf conf/matcha_tts.mas.v1.yaml] [--dumpdir dump]
@@ -58,11 +58,16 @@ precision=fp32        # fp32 = the reference's arithmetic; fp32_bf16x3 = f32 ten
 decode_batch_size=64  # utterances per ragged batch
 master_port=29517
 
+# evaluation related setting (stage 5)
+eval_metrics=""       # metrics of stage 5; empty: what this package computes (mcd); asr and sheet are refused by name
+eval_batch_size=16    # pairs per ragged batch
+
 # shellcheck disable=SC1091
 . "${REPO_ROOT}/egs/common/parse_options.sh" || exit 1
 . "${REPO_ROOT}/egs/common/stage1.sh" || exit 1
 . "${REPO_ROOT}/egs/common/stage3.sh" || exit 1
 . "${REPO_ROOT}/egs/common/stage4.sh" || exit 1
+. "${REPO_ROOT}/egs/common/stage5.sh" || exit 1
 
 set -euo pipefail
 
@@ -104,5 +109,6 @@ if [ "${stage}" -le 4 ] && [ "${stop_stage}" -ge 4 ]; then
 fi
 
 if [ "${stage}" -le 5 ] && [ "${stop_stage}" -ge 5 ]; then
-    log "Stage 5 (objective evaluation) is the reference recipe's own (evaluate.py on ${expdir}/results/*/${test_set}/wav)."
+    log "Stage 5: Objective evaluation"
+    stage5_evaluate
 fi

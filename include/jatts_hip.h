@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define JATTS_ABI_VERSION 7   /* (round 27 appended tap_group_n / tap_a0 / tap_b0 / tap_k to jatts_conv_desc WITHOUT a bump: the fields are a hint that every kernel may ignore, so a library from before them, which never reads that far, computes the same values; tests/test_attn_precision_cpu.py pins 7 -- a caller built against an older header must not be paired with this library: it would read the hint beyond the caller's struct) (round 15 added jatts_stft_mag, jatts_logmel_post, jatts_energy_frames, jatts_energy_adjust and jatts_token_average without a bump, as rounds 10, 11 and 13 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 13: jatts_hifigan_resunit / jatts_resunit_variant take w2 == NULL as the single-conv dilation unit, without a bump: no descriptor or signature changed, and a library from before it lacks jatts_resunit_single_conv, so it is refused when _abi.load binds that symbol) (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
+#define JATTS_ABI_VERSION 7   /* (round 29 added jatts_frame_select, jatts_gather_rows, jatts_pairwise_dist, jatts_dtw, jatts_dtw_path_stats and jatts_dtw_max_rows without a bump, as round 15 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 27 appended tap_group_n / tap_a0 / tap_b0 / tap_k to jatts_conv_desc WITHOUT a bump: the fields are a hint that every kernel may ignore, so a library from before them, which never reads that far, computes the same values; tests/test_attn_precision_cpu.py pins 7 -- a caller built against an older header must not be paired with this library: it would read the hint beyond the caller's struct) (round 15 added jatts_stft_mag, jatts_logmel_post, jatts_energy_frames, jatts_energy_adjust and jatts_token_average without a bump, as rounds 10, 11 and 13 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 13: jatts_hifigan_resunit / jatts_resunit_variant take w2 == NULL as the single-conv dilation unit, without a bump: no descriptor or signature changed, and a library from before it lacks jatts_resunit_single_conv, so it is refused when _abi.load binds that symbol) (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
                                 * so every descriptor that embeds it (jatts_conv_desc, jatts_resunit_desc, jatts_resblock_desc, jatts_relattn_desc) shifted by 8 bytes; JATTS_F32E; 2 (round 4): jatts_conv_desc + w_inv / act_a / act_b, jatts_resunit_desc + ws1 / ws2, jatts_resblock_desc + ws1 / ws2;
                                 * bumped whenever a descriptor's layout or an entry point's signature changes: a stale library is refused at load */
 
@@ -915,6 +915,41 @@ int jatts_alignment_logp_bwd(const jatts_ragged* rg_feats, const int32_t* cu_tex
  * Limits: T_text <= 1024 and T_feats * ceil(T_text / 64) * 8 bytes of decision bits must fit LDS. score may be NULL. */
 int jatts_mas_viterbi(const jatts_ragged* rg_feats, const int32_t* cu_text, const float* log_p, int32_t ld,
                       int32_t max_text_len, int64_t* path, int64_t* dur, double* score, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Stage 5, objective evaluation (csrc/evaluate.hip; appended without an ABI bump -- see JATTS_ABI_VERSION: no
+ * descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them).  Exact dynamic time
+ * warping with the frame selection in front of it and the sums along the path behind it; every entry is ragged over utterances or pairs,
+ * allocates nothing, uses no atomics and gives the same bits on every run.
+ *
+ * jatts_frame_select: per utterance over one f32 value per frame.  mode 0: frames with val > factor * mean (the mean in float64, summed
+ *   in a fixed order); mode 1: val > 0; mode 2: val > factor * max.  Modes 0 / 1: count[b] = number selected, idx[cu_rows[b] + k] = the k-th
+ *   selected frame (ascending, local to the utterance; the rest of the utterance's span is not written).  Mode 2: count[2 b] = first,
+ *   count[2 b + 1] = last selected frame (-1, -1 when none); idx may be NULL.  Comparisons are made in float64.
+ * jatts_gather_rows: dst[rg_out.cu_rows[b] + k][0 .. dim) = src[cu_src[b] + idx[cu_src[b] + k]][0 .. dim) for k < rg_out's length of b.
+ * jatts_pairwise_dist: per pair p (tab[5 p ..] = N, M, first row of a, first row of b, offset of c in floats):
+ *   c[i M + j] = sqrtf(sum_k (a_i[k] - b_j[k])^2), direct differences, f32, k ascending; dim <= 64.  max_n / max_m: the largest N / M.
+ * jatts_dtw: per pair p (tab[5 p ..] = N, M, offset of the N x M row-major f32 cost in floats, offset of the decision words in uint32,
+ *   offset of the path arrays in int32): D[0][0] = c[0][0], D[i][j] = c[i][j] + min(D[i-1][j-1], D[i-1][j], D[i][j-1]) in float64, ties to
+ *   the diagonal, then (i-1, j), then (i, j-1).  Writes path_len[p] = L, path_i / path_j [offset .. offset + L) in increasing order
+ *   (capacity N + M - 1) and total[p] = D[N-1][M-1].  decisions: N * ceil(M / 16) words of workspace per pair.  N <= jatts_dtw_max_rows()
+ *   (4096), else JATTS_ERR_UNSUPPORTED before the launch; a pair with N == 0 or M == 0 gets L = 0 and nothing else.
+ * jatts_dtw_path_stats: per pair p (tab[3 p ..] = first row of a / x, first row of b / y, offset of the path arrays) eight doubles
+ *   out[8 p ..] = L, sum sqrt(2 sum_k (a[k] - b[k])^2), sum x, sum y, sum x^2, sum y^2, sum x y, sum (x - y)^2 over the path, float64,
+ *   thread-strided then a fixed tree.  a / b (matrices) or x / y (tracks) may be NULL as a pair; the sums of the absent kind are 0.
+ * ------------------------------------------------------------------------------- */
+int32_t jatts_dtw_max_rows(void);
+int jatts_frame_select(const jatts_ragged* rg_frames, const float* val, int32_t mode, double factor, int32_t* count, int32_t* idx,
+                       void* stream);
+int jatts_gather_rows(const jatts_ragged* rg_out, const int32_t* cu_src, const int32_t* idx, const float* src, int32_t ld_src,
+                      int32_t dim, float* dst, int32_t ld_dst, void* stream);
+int jatts_pairwise_dist(int32_t n_pairs, const int64_t* tab, int32_t max_n, int32_t max_m, const float* a, int32_t lda, const float* b,
+                        int32_t ldb, int32_t dim, float* c, void* stream);
+int jatts_dtw(int32_t n_pairs, const int64_t* tab, int32_t max_n, const float* cost, uint32_t* decisions, int32_t* path_i,
+              int32_t* path_j, int32_t* path_len, double* total, void* stream);
+int jatts_dtw_path_stats(int32_t n_pairs, const int64_t* tab, const int32_t* path_i, const int32_t* path_j, const int32_t* path_len,
+                         const float* a, int32_t lda, const float* b, int32_t ldb, int32_t dim, const float* x, const float* y,
+                         double* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1508,6 +1508,159 @@ def f0_continuous_log(rb_frames, f0, use_continuous=True, use_log=True):
     return out
 
 
+# ---- stage-5 objective evaluation (csrc/evaluate.hip; host layer: jatts_amd/evaluate.py)
+SELECT_MEAN, SELECT_POSITIVE, SELECT_MAX = 0, 1, 2
+
+
+def frame_select(rb_frames, val, mode, factor=0.0, count=None):
+    """jatts_frame_select over one f32 value per frame.  SELECT_MEAN: val > factor * mean (float64), SELECT_POSITIVE: val > 0 -> (count int32
+    (n_seq,), idx int32 (rows,): the ascending local indices of utterance b at its frame offset).  SELECT_MAX: val > factor * max -> (int32
+    (n_seq, 2): first and last selected frame, -1 when none; None).  ``count``: an int32 device buffer to write into (a slice of one the
+    caller reads back once)."""
+    lib = _abi.load()
+    _f32d("frame_select", "a contiguous float32 value per frame", val, dims=(1,), numel=rb_frames.total)
+    if mode not in (SELECT_MEAN, SELECT_POSITIVE, SELECT_MAX):
+        raise ValueError(f"frame_select: unknown mode {mode}")
+    n = rb_frames.n_seq * (2 if mode == SELECT_MAX else 1)
+    if count is None:
+        count = torch.empty(n, dtype=torch.int32, device=val.device)
+    elif not count.is_cuda or count.dtype != torch.int32 or not count.is_contiguous() or count.numel() != n:
+        raise ValueError(f"frame_select: count must be a contiguous int32 device buffer of {n} elements")
+    idx = None if mode == SELECT_MAX else torch.empty(max(rb_frames.total, 1), dtype=torch.int32, device=val.device)
+    rg = rb_frames.struct()
+    with _Timed("frame_select", (mode, rb_frames.total)):
+        _abi.check(lib.jatts_frame_select(C.byref(rg), val.data_ptr(), int(mode), float(factor), count.data_ptr(), _ptr(idx), _stream()),
+                   "jatts_frame_select")
+    return (count.view(-1, 2), None) if mode == SELECT_MAX else (count, idx)
+
+
+def gather_rows(rb_src, idx, rb_out, src, dim=None):
+    """jatts_gather_rows: out[rb_out.cu[b] + k] = src[rb_src.cu[b] + idx[rb_src.cu[b] + k]] -> f32 (rb_out.total, dim), or (rb_out.total,)
+    for a 1-D ``src``.  ``idx``: what frame_select wrote for ``rb_src``; ``rb_out``: the geometry of its counts."""
+    lib = _abi.load()
+    _f32d("gather_rows", "contiguous float32 rows", src)
+    idx = _dev(idx)
+    flat = src.dim() == 1
+    ld = 1 if flat else src.shape[1]
+    dim = ld if dim is None else int(dim)
+    if idx.dtype != torch.int32 or idx.numel() < rb_src.total or src.numel() < rb_src.total * ld or rb_out.n_seq != rb_src.n_seq \
+            or any(o > s for o, s in zip(rb_out.lens, rb_src.lens)):
+        raise ValueError("gather_rows: an int32 index per source row and at most as many output rows per utterance expected")
+    out = torch.empty((rb_out.total,) if flat else (rb_out.total, dim), dtype=torch.float32, device=src.device)
+    if rb_out.total == 0:
+        return out
+    rg = rb_out.struct()
+    with _Timed("gather_rows", (rb_out.total, dim)):
+        _abi.check(lib.jatts_gather_rows(C.byref(rg), rb_src.cu.data_ptr(), idx.data_ptr(), src.data_ptr(), ld, dim, out.data_ptr(), dim, _stream()),
+                   "jatts_gather_rows")
+    return out
+
+
+def dtw_max_rows():
+    return int(_abi.load().jatts_dtw_max_rows())
+
+
+class PairGeometry:
+    """Host geometry of a batch of (a, b) sequence pairs for the DTW kernels: pair p = rows ``a_row0[p] .. + n[p]`` of one packed matrix
+    against rows ``b_row0[p] .. + m[p]`` of another.  Offsets of the per-pair cost matrices (floats), decision words (uint32) and path arrays
+    (int32, capacity n + m - 1) are laid out back to back, ``gap`` elements apart (tests put poison there)."""
+
+    def __init__(self, n, m, a_row0=None, b_row0=None, gap=0):
+        self.n, self.m = [int(v) for v in n], [int(v) for v in m]
+        if len(self.n) != len(self.m) or min(self.n + self.m, default=0) < 0:
+            raise ValueError("PairGeometry: one non-negative (n, m) per pair")
+        self.a_row0 = exclusive_scan(self.n)[:-1] if a_row0 is None else [int(v) for v in a_row0]
+        self.b_row0 = exclusive_scan(self.m)[:-1] if b_row0 is None else [int(v) for v in b_row0]
+        gap = int(gap)
+        self.c_off, self.d_off, self.p_off = [], [], []
+        c = d = p = gap
+        for a, b in zip(self.n, self.m):
+            self.c_off.append(c)
+            self.d_off.append(d)
+            self.p_off.append(p)
+            c += a * b + gap
+            d += a * ((b + 15) // 16) + gap
+            p += max(a + b - 1, 0) + gap
+        self.c_total, self.d_total, self.p_total = c, d, p
+        self.n_pairs, self.max_n, self.max_m = len(self.n), max(self.n, default=0), max(self.m, default=0)
+
+    def table(self, cols, device):
+        rows = {"n": self.n, "m": self.m, "a": self.a_row0, "b": self.b_row0, "c": self.c_off, "d": self.d_off, "p": self.p_off}
+        flat = [int(v) for vs in zip(*[rows[k] for k in cols]) for v in vs]
+        return h2d(flat or [0], torch.int64, device)
+
+
+def pairwise_dist(geo, a, b, dim=None, out=None):
+    """jatts_pairwise_dist: per pair the (n, m) row-major f32 matrix of Euclidean distances between rows of ``a`` and of ``b`` (row pitch
+    = their second dimension, ``dim`` <= 64 leading columns used), written at ``geo.c_off`` of one f32 buffer of ``geo.c_total``."""
+    lib = _abi.load()
+    _f32d("pairwise_dist", "contiguous float32 (rows, ld) matrices", a, b, dims=(2, 2))
+    dim = a.shape[1] if dim is None else int(dim)
+    if not 1 <= dim <= 64 or dim > a.shape[1] or dim > b.shape[1]:
+        raise ValueError("pairwise_dist: 1 <= dim <= 64 and dim <= the row pitches expected")
+    if any(r + n > a.shape[0] for r, n in zip(geo.a_row0, geo.n)) or any(r + m > b.shape[0] for r, m in zip(geo.b_row0, geo.m)):
+        raise ValueError("pairwise_dist: a pair reaches past its matrix")
+    if out is None:
+        out = torch.empty(max(geo.c_total, 1), dtype=torch.float32, device=a.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < geo.c_total:
+        raise ValueError("pairwise_dist: out must be a contiguous float32 device buffer of geo.c_total elements")
+    tab = geo.table("nmabc", a.device)
+    with _Timed("pairwise_dist", (geo.n_pairs, sum(n * m for n, m in zip(geo.n, geo.m)))):
+        _abi.check(lib.jatts_pairwise_dist(geo.n_pairs, tab.data_ptr(), geo.max_n, geo.max_m, a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1],
+                                           dim, out.data_ptr(), _stream()), "jatts_pairwise_dist")
+    return out
+
+
+def dtw(geo, cost, bufs=None):
+    """jatts_dtw on the cost matrices at ``geo.c_off`` of ``cost`` -> (path_len int32 (pairs,), path_i, path_j int32 (geo.p_total,): pair p's
+    path at geo.p_off[p], total float64 (pairs,)).  ValueError, before any launch, for a pair of more than dtw_max_rows() rows.  ``bufs``:
+    (decisions int32 (geo.d_total,), path_i, path_j, path_len, total) to write into (tests pass poisoned ones)."""
+    lib = _abi.load()
+    _f32d("dtw", "a contiguous float32 buffer of the pairs' cost matrices", cost, dims=(1,), numel=geo.c_total)
+    cap = dtw_max_rows()
+    if geo.max_n > cap:
+        raise ValueError(f"dtw: a pair has {geo.max_n} rows, the kernel takes at most {cap} (rows are the first sequence's frames)")
+    dev = cost.device
+    if bufs is None:
+        bufs = (torch.empty(max(geo.d_total, 1), dtype=torch.int32, device=dev), torch.empty(max(geo.p_total, 1), dtype=torch.int32, device=dev),
+                torch.empty(max(geo.p_total, 1), dtype=torch.int32, device=dev), torch.empty(max(geo.n_pairs, 1), dtype=torch.int32, device=dev),
+                torch.empty(max(geo.n_pairs, 1), dtype=torch.float64, device=dev))
+    dec, pi, pj, plen, total = (_dev(t) for t in bufs)
+    if dec.numel() < geo.d_total or min(pi.numel(), pj.numel()) < geo.p_total or min(plen.numel(), total.numel()) < geo.n_pairs \
+            or any(t.dtype != torch.int32 or not t.is_contiguous() for t in (dec, pi, pj, plen)) or total.dtype != torch.float64:
+        raise ValueError("dtw: workspace or output buffers too small or of the wrong type")
+    tab = geo.table("nmcdp", dev)
+    with _Timed("dtw", (geo.n_pairs, sum(n * m for n, m in zip(geo.n, geo.m)))):
+        _abi.check(lib.jatts_dtw(geo.n_pairs, tab.data_ptr(), geo.max_n, cost.data_ptr(), dec.data_ptr(), pi.data_ptr(), pj.data_ptr(),
+                                 plen.data_ptr(), total.data_ptr(), _stream()), "jatts_dtw")
+    return plen, pi, pj, total
+
+
+def dtw_path_stats(geo, path_len, path_i, path_j, a=None, b=None, dim=None, x=None, y=None, out=None):
+    """jatts_dtw_path_stats -> float64 (pairs, 8): L, sum sqrt(2 sum_c (a - b)^2), sum x, sum y, sum x^2, sum y^2, sum x y, sum (x - y)^2
+    along each pair's path; ``a`` / ``b``: the matrices the pairs index, ``x`` / ``y``: f32 tracks over the same rows."""
+    lib = _abi.load()
+    if (a is None) != (b is None) or (x is None) != (y is None) or (a is None and x is None):
+        raise ValueError("dtw_path_stats: two matrices, two tracks or both expected")
+    lda = ldb = d = 0
+    if a is not None:
+        _f32d("dtw_path_stats", "contiguous float32 (rows, ld) matrices", a, b, dims=(2, 2))
+        lda, ldb = a.shape[1], b.shape[1]
+        d = min(lda, ldb) if dim is None else int(dim)
+    if x is not None:
+        _f32d("dtw_path_stats", "contiguous float32 tracks", x, y, dims=(1, 1))
+    dev = path_i.device
+    if out is None:
+        out = torch.empty(max(geo.n_pairs, 1), 8, dtype=torch.float64, device=dev)
+    elif not out.is_cuda or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < 8 * geo.n_pairs:
+        raise ValueError("dtw_path_stats: out must be a contiguous float64 device buffer of 8 values per pair")
+    tab = geo.table("abp", dev)
+    with _Timed("dtw_path_stats", (geo.n_pairs, d)):
+        _abi.check(lib.jatts_dtw_path_stats(geo.n_pairs, tab.data_ptr(), _dev(path_i).data_ptr(), _dev(path_j).data_ptr(), _dev(path_len).data_ptr(),
+                                            _ptr(a), lda, _ptr(b), ldb, d, _ptr(x), _ptr(y), out.data_ptr(), _stream()), "jatts_dtw_path_stats")
+    return out
+
+
 # ---- stage-1 statistics (csrc/stats.hip; host layer: jatts_amd/features/stats.py)
 def col_moments_ws_doubles(rows, dim):
     """Doubles of workspace a col_moments call over ``rows`` rows needs: two sums per column and group of rows (include/jatts_hip.h)."""
