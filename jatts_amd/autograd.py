@@ -6,14 +6,117 @@ attention, which are plain batched GEMMs: jatts_bgemm (csrc/bgemm.hip, exact-f32
 is the FLOAT64 backward of the alignment module's distance matrix, AlignLogProb.backward, in the MAS-phase trainers).  All tensors are f32 and packed
 (rows, channels) row-major with a RaggedBatch describing the sequences; a padded batch is a RaggedBatch of equal lengths.
 Each Function names the reference module whose autograd it stands for.  No CPU fallback.
+
+Also here: the arithmetic those ops run on.  `arithmetic(precision, attention)` sets one precision.TrainArithmetic record around a step (the trainers
+do; exact f32 outside any context); Conv1dFunction -- the work-horse conv / linear op -- and BMM read it in their forward, decide their dtype codes
+there (conv_codes, emul_bgemm_wins) and carry them in ctx, so a backward launches what its forward decided.
 """
+import contextlib
+
 import torch
 
 from . import hip
-from .training import Conv1dFunction  # noqa: F401  (re-exported: the conv / linear op)
+from .precision import TrainArithmetic, train_arithmetic
 
 LN_EPS = 1e-12
 BN_EPS = 1e-5
+
+_ARITHMETIC = [TrainArithmetic(hip.F32, hip.F32)]
+
+
+@contextlib.contextmanager
+def arithmetic(precision, attention=None):
+    """Inside: Conv1dFunction and BMM run on precision.train_arithmetic(precision, attention) -- trainer names or a TrainArithmetic record.  An inner
+    context replaces the outer record whole; a captured graph bakes in whatever was on during its capture."""
+    prev, _ARITHMETIC[0] = _ARITHMETIC[0], train_arithmetic(precision, attention)
+    try:
+        yield
+    finally:
+        _ARITHMETIC[0] = prev
+
+
+def current_arithmetic():
+    return _ARITHMETIC[0]
+
+
+def emul_bgemm_wins(m, n, k):
+    """Dispatch rule of the emulated batched GEMM inside BMM: True only for the (m, n, k) classes where jatts_bgemm_emul measured faster than the
+    exact-f32 jatts_bgemm by more than the exact kernel's run-to-run spread; a shape inside the spread stays on exact f32, the more accurate of the two.
+    A function of the three GEMM dimensions alone: no batch size, no environment switch.  NO class has such a measurement yet (profiles/r10_notes.md), so
+    the rule routes nothing and attention="fp32_bf16x3" launches what "fp32" launches; the kernel stays reachable through hip.bgemm(dtype=hip.F32E)."""
+    return False
+
+
+def emul_wgrad_wins(c_in, n_out, k, rows):
+    """Dispatch rule of the emulated weight gradient inside the trainers: True where jatts_conv1d_wgrad_emul measured faster than the exact-f32 kernel by more
+    than the run-to-run spread (profiles/r07_notes.md, "Weight gradient on the bf16 pipe": spread 0.1 - 5 %, one 9.5 % outlier).  That is the WIDE pointwise
+    class only -- k = 1 with n_out c_in >= 2^20 at >= 4 096 rows (2048 x 512: 1.16x); the 384-wide k = 1 / k = 3 shapes gain 4 - 6 %, inside the spread, and
+    k = 5 loses 13 - 16 %, so they stay on the exact-f32 kernel, the more accurate of the two.  A function of the launch's shape alone; no environment switch."""
+    return k == 1 and rows >= 4096 and n_out * c_in >= (1 << 20)
+
+
+def conv_codes(operand, k, dil, c_in, n_out, rows):
+    """-> (dtype code of Conv1dFunction's forward and data-gradient convs, dtype code of its weight gradient) under the operand code `operand`: a halo
+    beyond the split / emulated kernels' tiles (hip.conv_halo_fits) puts all three on exact f32; the weight gradient leaves exact f32 only for an
+    emulated conv whose shape emul_wgrad_wins routes."""
+    code = operand if hip.conv_halo_fits(k, dil) else hip.F32
+    return code, hip.F32E if code == hip.F32E and emul_wgrad_wins(c_in, n_out, k, rows) else hip.F32
+
+
+class Conv1dFunction(torch.autograd.Function):
+    """y = conv1d(x) on a packed ragged batch (rows, c_in) -> (rows, n_out), f32; "same"-style geometry via (dil, pad).
+    forward: jatts_conv1d.  backward: dx = jatts_conv1d(dy, W'[c][n][k-1-tap], pad' = (k-1) dil - pad),
+    dW, db = jatts_conv1d_wgrad(x, dy) (the bias gradient falls out of the staged dy tiles).
+    The weight is re-packed on the device every step (hip.TrainWeight) for current_arithmetic().operand: exact f32, split f16 hi / lo (JATTS_F32S,
+    csrc/conv1d_split.h) or three exact bf16 terms, seven partial products (JATTS_F32E, csrc/conv1d_emul16.h); the code forward launched travels in ctx.geom."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, rb, dil, pad):
+        n_out, c_in, k = weight.shape
+        op = hip.TrainWeight(weight, current_arithmetic().operand)
+        xin = x.contiguous() if c_in == op.c_in else hip.affine_cast(x.contiguous(), hip.F32, ldy=op.c_in)
+        y = hip.conv1d(rb, xin, op, op.c_in, n_out, k, dtype=hip.F32, dil=dil, pad=pad,
+                       bias=None if bias is None else bias.detach().contiguous(), out_f32=True)
+        ctx.save_for_backward(x, weight)
+        ctx.geom = (rb, dil, pad, bias is not None, conv_codes(op.code, k, dil, c_in, n_out, x.shape[0])[0])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        rb, dil, pad, has_bias, code = ctx.geom
+        n_out, c_in, k = weight.shape
+        dy = dy.contiguous().float()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            # the data gradient is a conv like the forward, on the same arithmetic
+            op = hip.TrainWeight(weight, code, dgrad=True)       # W'[c][n][k-1-tap], packed in one launch
+            dyp = dy if n_out == op.c_in else hip.affine_cast(dy, hip.F32, ldy=op.c_in)
+            dx = hip.conv1d(rb, dyp, op, op.c_in, c_in, k, dtype=hip.F32, dil=dil, pad=(k - 1) * dil - pad, out_f32=True)
+        want_db = has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1]:
+            wcode = conv_codes(code, k, dil, c_in, n_out, x.shape[0])[1]
+            dw = hip.conv1d_wgrad(rb, x.detach().contiguous().float(), dy, c_in, n_out, k, dil, pad, want_db=want_db, dtype=wcode)
+            if want_db:
+                dw, db = dw
+        elif want_db:
+            db = hip.col_sum(dy)
+        return dx, dw, db, None, None, None
+
+
+class RaggedConv1d(torch.nn.Module):
+    """torch.nn.Conv1d's parameters (weight (n_out, c_in, k), bias) applied to packed ragged rows through Conv1dFunction."""
+
+    def __init__(self, c_in, n_out, k, dilation=1, padding=None, bias=True):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.empty(n_out, c_in, k))
+        self.bias = torch.nn.Parameter(torch.zeros(n_out)) if bias else None
+        torch.nn.init.xavier_uniform_(self.weight)
+        self.dil = dilation
+        self.pad = (k - 1) // 2 * dilation if padding is None else padding
+
+    def forward(self, rb, x):
+        return Conv1dFunction.apply(x, self.weight, self.bias, rb, self.dil, self.pad)
 
 
 class LayerNorm(torch.autograd.Function):
@@ -270,19 +373,18 @@ class BMM(torch.autograd.Function):
     """Batched matmul of the attention products on the exact-f32 matrix pipe (jatts_bgemm; round 4: these were torch.matmul -> rocBLAS):
     c = a @ b (trans_b False: b (..., k, n)) or a @ b^T (trans_b True: b (..., n, k)); a is (O, I, m, k), b is (O, I, ., .) or (I, ., .) --
     shared over O, as the position projection p_h is over the batch; its gradient is then summed over O.
-    Under training.emul_attention() each of the three products (forward, da, db) goes to the seven-product bf16x3 kernel (jatts_bgemm_emul) where
-    training.emul_bgemm_wins(m, n, k) says so for ITS dimensions; the three decisions are taken in forward and travel in ctx.codes, so backward
+    With current_arithmetic().attention F32E each of the three products (forward, da, db) goes to the seven-product bf16x3 kernel (jatts_bgemm_emul)
+    where emul_bgemm_wins(m, n, k) says so for ITS dimensions; the three decisions are taken in forward and travel in ctx.codes, so backward
     launches what forward decided whatever the context is by then."""
 
     @staticmethod
     def forward(ctx, a, b, trans_b):
-        from . import training      # (training imports the model code that imports this module)
         ctx.trans_b = bool(trans_b)
         ctx.save_for_backward(a, b)
         m, k = a.shape[-2], a.shape[-1]
         n = b.shape[-2] if ctx.trans_b else b.shape[-1]
-        if training.EMUL_ATTENTION[0]:
-            pick = lambda m_, n_, k_: hip.F32E if training.emul_bgemm_wins(m_, n_, k_) else hip.F32
+        if current_arithmetic().attention == hip.F32E:
+            pick = lambda m_, n_, k_: hip.F32E if emul_bgemm_wins(m_, n_, k_) else hip.F32
             # c: (m x n) over k | da = dc @ b^T or dc @ b: (m x k) over n | db = dc^T @ a: (n x k) over m, or a^T @ dc: (k x n) over m
             ctx.codes = (pick(m, n, k), pick(m, k, n), pick(n, k, m) if ctx.trans_b else pick(k, n, m))
         else:

@@ -632,6 +632,37 @@ def pack_conv_weight_bf16x3_dev(w, c_mult=64, dgrad=False):
     return out, c_pad
 
 
+class TrainWeight(PreparedWeight):
+    """A conv weight that changes every step (training): a device f32 weight (n_out, c_in, k) for operand code F32 / F32S / F32E, packed by the device
+    packers above; dgrad=True: the data-gradient operand W'[c][n][k-1-tap].  ``c_in`` is the padded c_in of the packed conv.  Packs lazily and only
+    the form hip.conv1d launches: ``packed`` / ``inv`` where the halo fits, f32() where it does not -- one packing per conv either way."""
+
+    def __init__(self, w, code, dgrad=False, c_mult=64):
+        if code not in (F32, F32S, F32E):
+            raise ValueError(f"TrainWeight: operand code {code} (F32, F32S or F32E)")
+        super().__init__(w, c_mult)
+        self.code, self.layout, self._dgrad, self._pair = code, int(code == F32E), dgrad, None      # (jatts_conv_desc.w_layout 1: the F32E device packing)
+        self.c_in = round_up(w.shape[0 if dgrad else 1], c_mult)
+
+    def _pack(self):
+        if self._pair is None:
+            if self.code == F32S:
+                self._pair = pack_conv_weight_split_dev(self._src, self._c_mult, self._dgrad)[:2]
+            elif self.code == F32E:
+                self._pair = (pack_conv_weight_bf16x3_dev(self._src, self._c_mult, self._dgrad)[0], None)
+            else:
+                self._pair = (self.f32(), None)
+        return self._pair
+
+    packed = property(lambda self: self._pack()[0])
+    inv = property(lambda self: self._pack()[1])
+
+    def f32(self):
+        if self._f32 is None:
+            self._f32 = pack_conv_weight_dev(self._src, F32, self._c_mult, self._dgrad)[0]
+        return self._f32
+
+
 def _polyphase_taps(K, stride, padding):
     """The (phase r, input offset q) pairs of ConvTranspose1d(K, stride, padding): output step j * stride + r takes w[..., stride * q + r + padding] from
     input row j - q.  -> (pairs, qmin, qmax); the polyphase conv holds the pair (r, q) at tap qmax - q."""

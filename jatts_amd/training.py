@@ -1,196 +1,18 @@
-"""Training-side pieces on the MI355X path -- the first slice of SURVEY §8 f.4 (reference
-jatts/trainers/fastspeech2.py:24-100 `_train_step`, jatts/bin/tts_train.py:355-363 DistributedDataParallel).
+"""The trainers of the MI355X path (reference jatts/trainers/*.py `_train_step`, jatts/bin/tts_train.py) and stage 3 around them.
 
-What is here: (1) the FastSpeech2 criterion (`MelLoss`/`L1Loss`, `DurationPredictorLoss`, `PitchLoss`, `EnergyLoss` of
-jatts/losses/) evaluated by HIP kernels on the dict that `FastSpeech2.forward()` returns, i.e. `_train_step` up to `gen_loss`;
-(2) the backward of the hot path's work-horse op: `Conv1dFunction`, a torch.autograd.Function whose forward is jatts_conv1d and
-whose backward is three HIP launches (dx = jatts_conv1d on flipped / transposed weights, dW = jatts_conv1d_wgrad, db =
-jatts_col_sum), in f32; (3) `allreduce_gradients`: bucketed, flat gradient all-reduce over RCCL (what DDP does for the
-reference), usable after any backward; (4) `FastSpeech2Trainer`: the whole `_train_step` -- FastSpeech2.forward() in train()
-mode (models/fastspeech2_train.py on the HIP forward / backward pairs of jatts_amd/autograd.py), the criterion, backward, the
-gradient all-reduce, clip_grad_norm_ + Adam as HIP kernels, the reference's WarmupLR schedule.  What is NOT here yet: the
-training paths of Matcha-TTS / VITS, f16 training.  No CPU fallback: CPU tensors raise.
+What is here: (1) the gradient exchange: `allreduce_gradients` / `allreduce_flat`, bucketed all-reduce over RCCL (what DistributedDataParallel does for
+the reference), and its overlap with backward inside the trainers; (2) the learning-rate schedules (WarmupLR, StepLR); (3) `FastSpeech2Trainer`: the
+whole `_train_step` -- forward in train() mode (models/*_train.py on the HIP forward / backward pairs of jatts_amd/autograd.py), the criterion,
+backward, the gradient all-reduce, clip_grad_norm_ + Adam as HIP kernels on flat buffers, checkpoints in the reference's format, and the step captured
+and replayed as a hipGraph per batch signature -- with `MatchaTTSTrainer` (tts1 and the MAS model) and `VITSTrainer` derived from it; (4) stage 3:
+recipe config -> trainer (`trainer_kwargs`, refusals by name) and the training loop.  A trainer's arithmetic is one precision.TrainArithmetic record
+(`precision=` / `attention=`), set around every step with autograd.arithmetic.  f32 tensors only.  No CPU fallback: CPU tensors raise.
 """
-import contextlib
-
 import torch
 import torch.distributed as dist
 
-from . import graphs, hip
-
-L1, L2 = 0, 1
-
-
-# ------------------------------------------------------------------------------------------ criterion
-@torch.no_grad()
-def fastspeech2_losses(ret, durations, pitch, energy, ilens, use_masking=True):
-    """`_train_step`'s loss block (trainers/fastspeech2.py:62-84) on FastSpeech2.forward()'s return dict.
-    -> dict(mel_loss, duration_loss, pitch_loss, energy_loss, loss), f32 scalars on the GPU.
-    MelLoss = L1(before, ys) + L1(after, ys) over the frames t < olens (mean over selected elements, l1l2_loss.py:43-63);
-    DurationPredictorLoss = MSE(d_outs, log(ds + 1)) over tokens t < ilens; Pitch / EnergyLoss = MSE over t < ilens."""
-    before, after, ys, olens = ret["before_outs"], ret["after_outs"], ret["ys"], ret["olens"]
-    dev = before.device
-    B, To, od = before.shape
-    Tm = ret["d_outs"].shape[1]
-    rbo, rbt = hip.RaggedBatch([To] * B, dev), hip.RaggedBatch([Tm] * B, dev)
-    vo = olens.to(device=dev, dtype=torch.int32) if use_masking else None
-    vi = ilens.to(device=dev, dtype=torch.int32) if use_masking else None
-    n_o = float(int(olens.sum()) if use_masking else B * To) * od
-    n_i = float(int(ilens.sum()) if use_masking else B * Tm)
-    ys2 = ys.to(dev).float().reshape(B * To, od).contiguous()
-    mel = hip.masked_loss(rbo, before.reshape(B * To, od), ys2, vo, L1, 1.0 / n_o)
-    if after is not None:
-        mel = mel + hip.masked_loss(rbo, after.reshape(B * To, od), ys2, vo, L1, 1.0 / n_o)
-    flat = lambda t: t.to(dev).float().reshape(B * Tm, 1).contiguous()  # noqa: E731
-    dur = hip.masked_loss(rbt, flat(ret["d_outs"]), flat(durations[:, :Tm]), vi, L2, 1.0 / n_i, log_offset=1.0)
-    pit = hip.masked_loss(rbt, flat(ret["p_outs"]), flat(pitch[:, :Tm]), vi, L2, 1.0 / n_i)
-    ene = hip.masked_loss(rbt, flat(ret["e_outs"]), flat(energy[:, :Tm]), vi, L2, 1.0 / n_i)
-    return dict(mel_loss=mel, duration_loss=dur, pitch_loss=pit, energy_loss=ene, loss=mel + dur + pit + ene)
-
-
-# ------------------------------------------------------------------------------------------ conv1d with a backward
-# precision="fp32_split" of the trainers (round 4): the forward and data-gradient convs of every Conv1dFunction on split-precision MFMA operands
-# (JATTS_F32S, csrc/conv1d_split.h); weight gradients, normalisations, attention products and the optimiser stay exact f32.  Module-level
-# switch set around a step by the trainer (split_convs()); a captured graph bakes in whatever was on during its capture.
-SPLIT_CONVS = [False]
-
-
-@contextlib.contextmanager
-def _switched(flag, on):
-    prev, flag[0] = flag[0], bool(on)
-    try:
-        yield
-    finally:
-        flag[0] = prev
-
-
-def split_convs(on=True):
-    return _switched(SPLIT_CONVS, on)
-
-
-# precision="fp32_bf16x3" of the trainers (round 7): the same convs on the f32-EQUIVALENT emulated arithmetic (JATTS_F32E: three exact bf16 terms per
-# operand, seven partial products, csrc/conv1d_emul16.h) with the weight re-packed on the device every step (jatts_pack_conv_weight_bf16x3), and the WEIGHT
-# gradient on the same arithmetic where the dispatch rule below routes it (jatts_conv1d_wgrad_emul).  A switch of its own: SPLIT_CONVS / split_convs() keep
-# their meaning; with both on, the emulated mode wins.
-EMUL_CONVS = [False]
-
-# the trainers' precisions -> which contractions leave exact f32 (FastSpeech2Trainer.__init__ builds its error message from this)
-TRAIN_PRECISIONS = {
-    "fp32": "exact-f32 MFMA, the reference's arithmetic",
-    "fp32_split": "f32 tensors; the forward and data-gradient convs on split f16 hi / lo MFMA operands, everything else exact f32",
-    "fp32_bf16x3": "f32 tensors; the forward, data-gradient and weight-gradient convs on three exact bf16 terms per operand (seven partial products, "
-                   "f32-equivalent), everything else exact f32",
-}
-
-
-def emul_convs(on=True):
-    return _switched(EMUL_CONVS, on)
-
-
-# attention="fp32_bf16x3" of the trainers (round 10): the attention products of autograd.BMM -- q k^T, q p^T, P v, the Gaussian-upsampling p_up @ hs (while autograd.MAS_OWN_KERNELS leaves it on BMM) and their
-# gradients -- on the same emulated arithmetic (jatts_bgemm_emul) where emul_bgemm_wins routes them.  A switch of its own, independent of the conv modes.
-EMUL_ATTENTION = [False]
-TRAIN_ATTENTIONS = {
-    "fp32": "exact-f32 MFMA (the default, also None)",
-    "fp32_bf16x3": "three exact bf16 terms per operand, seven partial products, for the product shapes emul_bgemm_wins routes; exact f32 elsewhere",
-}
-
-
-def emul_attention(on=True):
-    return _switched(EMUL_ATTENTION, on)
-
-
-def emul_bgemm_wins(m, n, k):
-    """Dispatch rule of the emulated batched GEMM inside autograd.BMM: True only for the (m, n, k) classes where jatts_bgemm_emul measured faster than the
-    exact-f32 jatts_bgemm by more than the exact kernel's run-to-run spread; a shape inside the spread stays on exact f32, the more accurate of the two.
-    A function of the three GEMM dimensions alone: no batch size, no environment switch.  NO class has such a measurement yet (profiles/r10_notes.md), so
-    the rule routes nothing and attention="fp32_bf16x3" launches what "fp32" launches; the kernel stays reachable through hip.bgemm(dtype=hip.F32E)."""
-    return False
-
-
-@contextlib.contextmanager
-def precision_convs(precision):
-    """The conv mode of a trainer precision around a step: split_convs() for "fp32_split", emul_convs() for "fp32_bf16x3"."""
-    with split_convs(precision == "fp32_split"), emul_convs(precision == "fp32_bf16x3"):
-        yield
-
-
-def emul_wgrad_wins(c_in, n_out, k, rows):
-    """Dispatch rule of the emulated weight gradient inside the trainers: True where jatts_conv1d_wgrad_emul measured faster than the exact-f32 kernel by more
-    than the run-to-run spread (profiles/r07_notes.md, "Weight gradient on the bf16 pipe": spread 0.1 - 5 %, one 9.5 % outlier).  That is the WIDE pointwise
-    class only -- k = 1 with n_out c_in >= 2^20 at >= 4 096 rows (2048 x 512: 1.16x); the 384-wide k = 1 / k = 3 shapes gain 4 - 6 %, inside the spread, and
-    k = 5 loses 13 - 16 %, so they stay on the exact-f32 kernel, the more accurate of the two.  A function of the launch's shape alone; no environment switch."""
-    return k == 1 and rows >= 4096 and n_out * c_in >= (1 << 20)
-
-
-def _pack_conv_operand(mode, weight, dgrad):
-    """The per-step device packing of Conv1dFunction's weight in mode 0 / 1 / 2 (exact f32 / split / emulated); dgrad: the data-gradient operand
-    W'[c][n][k-1-tap].  -> (packed, padded c_in, dtype code, inverse scales or None, w_layout)."""
-    w = weight.detach()
-    if mode == 2:
-        return (*hip.pack_conv_weight_bf16x3_dev(w, dgrad=dgrad), hip.F32E, None, 1)
-    if mode == 1:
-        wp, winv, c_pad = hip.pack_conv_weight_split_dev(w, dgrad=dgrad)
-        return wp, c_pad, hip.F32S, winv, 0
-    return (*hip.pack_conv_weight_dev(w, hip.F32, dgrad=dgrad), hip.F32, None, 0)
-
-
-class Conv1dFunction(torch.autograd.Function):
-    """y = conv1d(x) on a packed ragged batch (rows, c_in) -> (rows, n_out), f32; "same"-style geometry via (dil, pad).
-    forward: jatts_conv1d.  backward: dx = jatts_conv1d(dy, W'[c][n][k-1-tap], pad' = (k-1) dil - pad),
-    dW, db = jatts_conv1d_wgrad(x, dy) (the bias gradient falls out of the staged dy tiles).
-    Three modes: exact f32, split (SPLIT_CONVS) and emulated (EMUL_CONVS); mode 0 / 1 / 2 travels in ctx.geom."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, rb, dil, pad):
-        n_out, c_in, k = weight.shape
-        fits = hip.conv_halo_fits(k, dil)                     # (beyond the split / emulated kernels' tiles: the exact-f32 kernel)
-        mode = 2 if EMUL_CONVS[0] and fits else 1 if SPLIT_CONVS[0] and fits else 0
-        wp, c_pad, code, winv, layout = _pack_conv_operand(mode, weight, False)
-        xin = x.contiguous() if c_in == c_pad else hip.affine_cast(x.contiguous(), hip.F32, ldy=c_pad)
-        y = hip.conv1d(rb, xin, wp, c_pad, n_out, k, dtype=code, dil=dil, pad=pad,
-                       bias=None if bias is None else bias.detach().contiguous(), w_inv=winv, out_f32=True, w_layout=layout)
-        ctx.save_for_backward(x, weight)
-        ctx.geom = (rb, dil, pad, bias is not None, mode, EMUL_CONVS[0])
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        rb, dil, pad, has_bias, mode, emul_on = ctx.geom
-        n_out, c_in, k = weight.shape
-        dy = dy.contiguous().float()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            # the data gradient is a conv like the forward: same arithmetic (split: the WEIGHT gradient below stays exact f32)
-            wp, c_pad, code, winv, layout = _pack_conv_operand(mode, weight, True)       # W'[c][n][k-1-tap], packed in one launch
-            dyp = dy if n_out == c_pad else hip.affine_cast(dy, hip.F32, ldy=c_pad)
-            dx = hip.conv1d(rb, dyp, wp, c_pad, c_in, k, dtype=code, dil=dil, pad=(k - 1) * dil - pad, w_inv=winv, out_f32=True, w_layout=layout)
-        want_db = has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1]:
-            # emulated mode: the weight gradient on the same arithmetic where the shape rule says it is the faster kernel (a halo beyond 32 rows never is)
-            wcode = hip.F32E if emul_on and hip.conv_halo_fits(k, dil) and emul_wgrad_wins(c_in, n_out, k, x.shape[0]) else hip.F32
-            dw = hip.conv1d_wgrad(rb, x.detach().contiguous().float(), dy, c_in, n_out, k, dil, pad, want_db=want_db, dtype=wcode)
-            if want_db:
-                dw, db = dw
-        elif want_db:
-            db = hip.col_sum(dy)
-        return dx, dw, db, None, None, None
-
-
-class RaggedConv1d(torch.nn.Module):
-    """torch.nn.Conv1d's parameters (weight (n_out, c_in, k), bias) applied to packed ragged rows through Conv1dFunction."""
-
-    def __init__(self, c_in, n_out, k, dilation=1, padding=None, bias=True):
-        super().__init__()
-        self.weight = torch.nn.Parameter(torch.empty(n_out, c_in, k))
-        self.bias = torch.nn.Parameter(torch.zeros(n_out)) if bias else None
-        torch.nn.init.xavier_uniform_(self.weight)
-        self.dil = dilation
-        self.pad = (k - 1) // 2 * dilation if padding is None else padding
-
-    def forward(self, rb, x):
-        return Conv1dFunction.apply(x, self.weight, self.bias, rb, self.dil, self.pad)
+from . import autograd, graphs, hip, precision as _precision
+from .precision import TRAIN_ATTENTIONS, TRAIN_PRECISIONS  # noqa: F401  (read by the CLI under these names)
 
 
 # ------------------------------------------------------------------------------------------ gradient exchange
@@ -302,12 +124,8 @@ class FastSpeech2Trainer:
     def __init__(self, model, lr=0.0008, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_norm=1.0, warmup_steps=4000, group=None,
                  bucket_bytes=64 << 20, overlap=True, gradient_accumulate_steps=1, scheduler="warmuplr", scheduler_params=None, capture_graph=False,
                  max_graphs=8, precision="fp32", attention=None):
-        if precision not in TRAIN_PRECISIONS:
-            raise ValueError(f"trainer precision {precision!r}: " + " or ".join(f"{k!r} ({v})" for k, v in TRAIN_PRECISIONS.items()))
-        if attention is not None and attention not in TRAIN_ATTENTIONS:
-            raise ValueError(f"trainer attention {attention!r}: None or " + " or ".join(f"{k!r} ({v})" for k, v in TRAIN_ATTENTIONS.items()))
-        self.precision = precision
-        self.attention = attention      # the attention products' arithmetic, independent of `precision` (emul_attention / emul_bgemm_wins)
+        self.arith = _precision.train_arithmetic(precision, attention)      # (raises for an unknown name, before the model is touched)
+        self.precision, self.attention = precision, attention               # the names, as given
         self.model, self.base_lr, self.betas, self.eps, self.wd = model, lr, betas, eps, weight_decay
         self.grad_norm, self.warmup_steps, self.group, self.bucket_bytes = grad_norm, warmup_steps, group, bucket_bytes
         self.overlap = overlap
@@ -513,7 +331,7 @@ class FastSpeech2Trainer:
         was = self.model.training
         self.model.eval()
         try:
-            with precision_convs(self.precision), emul_attention(self.attention == "fp32_bf16x3"):
+            with autograd.arithmetic(self.arith):
                 return {k: v.detach() for k, v in self.compute_losses(batch).items()}
         finally:
             self.model.train(was)
@@ -621,7 +439,7 @@ class FastSpeech2Trainer:
         self.model.train()
         self._phase = self._loss_phase()
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
-        with precision_convs(self.precision), emul_attention(self.attention == "fp32_bf16x3"):      # around the eager, capturing and replaying forms
+        with autograd.arithmetic(self.arith):      # around the eager, capturing and replaying forms
             if self.capture_graph and not multi and self.accumulate == 1:
                 sig = self._signature(batch)
                 if sig not in self._graphs and batch.get("durations") is not None:      # first sight of this bucket: verify the frame counts

@@ -267,7 +267,8 @@ def check_exact(y, want, what=""):
 
 
 # backward / weight-gradient tables
-BACKWARD_GEOMS = [(4, 1, 2), (2, 1, 1), (3, 1, 0), (5, 2, 8), (7, 3, 5)]
+BACKWARD_GEOMS = [(4, 1, 2), (2, 1, 1), (3, 1, 0), (5, 2, 8), (7, 3, 5),
+                  (3, 17, 17), (5, 9, 4)]      # halo 34 / 36: beyond the split and emulated kernels' 32 rows (hip.conv_halo_fits)
 WGRAD_GEOMS = [(1, 1, 0), (3, 1, 0), (3, 1, 2), (5, 2, 8), (5, 2, 3),      # the MFMA path (k 1 / 3 / 5)
                (2, 1, 1), (2, 1, 0), (4, 1, 2), (7, 3, 5)]                   # the VALU path
 WGRAD_SHAPES = [(64, 72), (192, 160)]                                        # (c_in, n_out)

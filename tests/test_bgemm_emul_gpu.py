@@ -1,5 +1,5 @@
 """The training attention products on the fp32_bf16x3 arithmetic (round 10): jatts_bgemm_emul (the per-product bound, fp64 references over every tile,
-edge and load path, batch indexing, determinism across tile variants, refusals), autograd.BMM under training.emul_attention() and the whole train steps
+edge and load path, batch indexing, determinism across tile variants, refusals), autograd.BMM under autograd.arithmetic(attention="fp32_bf16x3") and the whole train steps
 of the four trainers with attention="fp32_bf16x3" and the routing forced on -- at the tolerances the existing tests apply to exact f32."""
 import ctypes as C
 import json
@@ -140,9 +140,10 @@ def test_bgemm_emul_refusals(cuda, lib):
 def test_bmm_under_emul_attention(cuda, lib, monkeypatch, trans_b, shared):
     """Routing forced on: output and both gradients against float64 autograd at 2e-6; a backward run after the context has exited still takes the emulated
     kernel (its results equal those of direct hip.bgemm(dtype=F32E) calls, and the launches are counted); with the context off BMM is today's BMM."""
-    from jatts_amd import hip, training
-    from jatts_amd.autograd import BMM
-    monkeypatch.setattr(training, "emul_bgemm_wins", lambda m, n, k: True)
+    from jatts_amd import autograd, hip
+    from jatts_amd.autograd import BMM, arithmetic, current_arithmetic
+    from jatts_amd.precision import TrainArithmetic
+    monkeypatch.setattr(autograd, "emul_bgemm_wins", lambda m, n, k: True)
     O, I, m, n, k = 2, 2, 70, 48, 33
     g = torch.Generator().manual_seed(5 + trans_b + 2 * shared)
     a = torch.randn(O, I, m, k, generator=g)
@@ -154,9 +155,9 @@ def test_bmm_under_emul_attention(cuda, lib, monkeypatch, trans_b, shared):
     calls = []
     real = hip.bgemm
     monkeypatch.setattr(hip, "bgemm", lambda *x, **kw: (calls.append(kw.get("dtype", hip.F32)), real(*x, **kw))[1])
-    with training.emul_attention():
+    with arithmetic("fp32", attention="fp32_bf16x3"):
         y = BMM.apply(ad, bd, trans_b)
-    assert not training.EMUL_ATTENTION[0]
+    assert current_arithmetic() == TrainArithmetic(hip.F32, hip.F32)
     y.backward(gy.to(cuda))                       # after the context: what forward decided
     assert calls == [hip.F32E] * 3, calls
     yr = (ar @ (br.transpose(-1, -2) if trans_b else br)).detach()
@@ -167,7 +168,7 @@ def test_bmm_under_emul_attention(cuda, lib, monkeypatch, trans_b, shared):
     # context off (patched rule or not): today's BMM, bit for bit
     del calls[:]
     a2, b2 = a.to(cuda).requires_grad_(), b.to(cuda).requires_grad_()
-    with training.emul_attention(False):
+    with arithmetic("fp32"):
         y2 = BMM.apply(a2, b2, trans_b)
     y2.backward(gy.to(cuda))
     assert calls == [hip.F32] * 3
@@ -181,8 +182,8 @@ def test_bmm_under_emul_attention(cuda, lib, monkeypatch, trans_b, shared):
 # ------------------------------------------------------------------------------------------ whole train steps, attention="fp32_bf16x3", routing forced on
 @pytest.fixture
 def forced(monkeypatch):
-    from jatts_amd import hip, training
-    monkeypatch.setattr(training, "emul_bgemm_wins", lambda m, n, k: True)
+    from jatts_amd import autograd, hip
+    monkeypatch.setattr(autograd, "emul_bgemm_wins", lambda m, n, k: True)
     seen = []
     real = hip.bgemm
     monkeypatch.setattr(hip, "bgemm", lambda *x, **kw: (seen.append(kw.get("dtype", hip.F32)), real(*x, **kw))[1])
@@ -196,7 +197,8 @@ def test_fastspeech2_train_step_with_emulated_attention(cuda, lib, forced, preci
     from jatts_amd import hip
     from jatts_amd.models import FastSpeech2
     from jatts_amd.models.fastspeech2_train import criterion
-    from jatts_amd.training import FastSpeech2Trainer, emul_attention, precision_convs
+    from jatts_amd.autograd import arithmetic
+    from jatts_amd.training import FastSpeech2Trainer
     z, zi, keys, cfg = _fs2_golden()
     m = FastSpeech2(idim=20, **{**FS2_SMALL, **cfg})
     sd0 = golden_state(keys, 0)
@@ -209,7 +211,7 @@ def test_fastspeech2_train_step_with_emulated_attention(cuda, lib, forced, preci
     tr = FastSpeech2Trainer(m, lr=0.0008, grad_norm=1.0, warmup_steps=4000, precision=precision, attention="fp32_bf16x3")
     assert tr.attention == "fp32_bf16x3" and tr.precision == precision
     m.train()
-    with precision_convs(precision), emul_attention():
+    with arithmetic(precision, attention="fp32_bf16x3"):
         ret = m(batch["xs"], il, batch["ys"], ol, batch["durations"], il, batch["pitch"], il, batch["energys"], il)
         for k in ("before_outs", "after_outs", "d_outs", "p_outs", "e_outs"):
             assert relerr(ret[k].detach(), z["ref_" + k]) <= 2e-5, (k, relerr(ret[k].detach(), z["ref_" + k]))
@@ -256,7 +258,8 @@ def test_matcha_train_step_with_emulated_attention(cuda, lib, forced, which, pre
     from jatts_amd.models import MatchaTTS, MatchaTTS_MAS
     from jatts_amd.models.matchatts_train import criterion
     from jatts_amd.synthetic import matcha_golden_tweaks
-    from jatts_amd.training import MatchaTTSTrainer, emul_attention, precision_convs
+    from jatts_amd.autograd import arithmetic
+    from jatts_amd.training import MatchaTTSTrainer
     tts1 = which == "tts1"
     z, keys = load_golden("matcha_tts1_train_small.npz" if tts1 else "matcha_mas_train_small.npz")
     zi, _ = load_golden("matcha_tts1_forward_small.npz" if tts1 else "matcha_forward_small.npz")
@@ -266,7 +269,7 @@ def test_matcha_train_step_with_emulated_attention(cuda, lib, forced, which, pre
     assert MatchaTTSTrainer(m, precision=precision, attention="fp32_bf16x3").attention == "fp32_bf16x3"
     t = lambda k: torch.tensor(zi[k])  # noqa: E731
     il, ol = t("text_lengths"), t("feats_lengths")
-    with precision_convs(precision), emul_attention():
+    with arithmetic(precision, attention="fp32_bf16x3"):
         if tts1:
             ret = m(t("text"), il, t("feats"), ol, t("durations"), il, cfm_t=t("t"), cfm_noise=t("z"))
             assert relerr(ret["d_outs"].detach(), z["ref_d_outs"]) <= 2e-5
@@ -290,7 +293,8 @@ def test_vits_train_step_with_emulated_attention(cuda, lib, forced, precision):
     from jatts_amd import hip
     from jatts_amd.models import VITS
     from jatts_amd.models.vits_train import criterion
-    from jatts_amd.training import VITSTrainer, emul_attention, precision_convs
+    from jatts_amd.autograd import arithmetic
+    from jatts_amd.training import VITSTrainer
     z, keys = load_golden("vits_train_small.npz")
     zi, _ = load_golden("vits_forward_small.npz")
     m = VITS(idim=20, **json.loads(str(z["config"])))
@@ -299,7 +303,7 @@ def test_vits_train_step_with_emulated_attention(cuda, lib, forced, precision):
     assert VITSTrainer(m, precision=precision, attention="fp32_bf16x3").attention == "fp32_bf16x3"
     t = lambda k: torch.tensor(zi[k])  # noqa: E731
     il, ol = t("text_lengths"), t("feats_lengths")
-    with precision_convs(precision), emul_attention():
+    with arithmetic(precision, attention="fp32_bf16x3"):
         ret = m(t("text"), il, t("feats"), ol, spembs=t("spembs"), post_noise=t("noise"))
         assert torch.equal(ret["ds"].cpu(), torch.tensor(z["ref_ds"]))
         losses = criterion(ret, il, ol, duration_loss=True, forward_sum=True, bin_loss=True, lambda_align=2.0)
@@ -338,8 +342,8 @@ def test_graph_mode_replays_the_same_training_with_emulated_attention(cuda, lib,
 
 def test_default_attention_is_untouched(cuda, lib, monkeypatch):
     """attention=None with the routing patched to True: one FastSpeech2 step's losses and every gradient are torch.equal to a step taken with the
-    emul_attention context never entered -- and no emulated launch happens."""
-    from jatts_amd import hip, training
+    arithmetic context never entered -- and no emulated launch happens."""
+    from jatts_amd import autograd, hip
     from jatts_amd.models import FastSpeech2
     from jatts_amd.training import FastSpeech2Trainer
     z, zi, keys, cfg = _fs2_golden()
@@ -356,7 +360,7 @@ def test_default_attention_is_untouched(cuda, lib, monkeypatch):
         lr_ = ref._train_step(batch)
     finally:
         hip.zero_pool_end()
-    monkeypatch.setattr(training, "emul_bgemm_wins", lambda m, n, k: True)
+    monkeypatch.setattr(autograd, "emul_bgemm_wins", lambda m, n, k: True)
     seen = []
     real = hip.bgemm
     monkeypatch.setattr(hip, "bgemm", lambda *x, **kw: (seen.append(kw.get("dtype", hip.F32)), real(*x, **kw))[1])

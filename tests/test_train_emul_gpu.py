@@ -67,11 +67,11 @@ def _wgrad_ref64(x, dy, lens, k, dil, pad):
 @pytest.mark.parametrize("c_in,n_out,k,dil,lens", [(64, 96, 3, 1, [70, 5, 33]), (80, 64, 5, 2, [40, 41]), (128, 128, 1, 1, [129]),
                                                    (48, 20, 7, 3, [64, 30]), (192, 320, 5, 1, [300, 257, 64, 1]), (384, 200, 3, 1, [768, 500])])
 def test_conv1d_backward_in_the_emulated_mode_matches_autograd(cuda, lib, c_in, n_out, k, dil, lens):
-    """test_conv1d_backward_matches_autograd's shapes and seeds through Conv1dFunction under emul_convs(): y, dx, dW, db within the exact-f32 path's
+    """test_conv1d_backward_matches_autograd's shapes and seeds through Conv1dFunction under arithmetic("fp32_bf16x3"): y, dx, dW, db within the exact-f32 path's
     2e-5 of fp64 autograd; the emulated weight-gradient kernel itself (whatever the trainer's shape rule routes) held to the same 2e-5 and to
     max|dW_emul - dW_64| <= 2 max|dW_f32 - dW_64| (acceptance rule (3) of DESIGN §4, against the existing exact-f32 kernel)."""
     from jatts_amd import hip
-    from jatts_amd.training import Conv1dFunction, emul_convs
+    from jatts_amd.autograd import Conv1dFunction, arithmetic
     g = torch.Generator().manual_seed(c_in + n_out + k)
     R = sum(lens)
     x = torch.randn(R, c_in, generator=g)
@@ -88,7 +88,7 @@ def test_conv1d_backward_in_the_emulated_mode_matches_autograd(cuda, lib, c_in, 
     yr.backward(gy.double())
     xd, wd, bd = x.to(cuda).requires_grad_(), w.to(cuda).requires_grad_(), b.to(cuda).requires_grad_()
     rb = hip.RaggedBatch(lens, cuda)
-    with emul_convs():
+    with arithmetic("fp32_bf16x3"):
         y = Conv1dFunction.apply(xd, wd, bd, rb, dil, pad)
         y.backward(gy.to(cuda))
     errs = dict(y=relerr(y.detach(), yr.detach()), dx=relerr(xd.grad, xr.grad), dw=relerr(wd.grad, wr.grad), db=relerr(bd.grad, br.grad))
@@ -188,7 +188,8 @@ def test_fastspeech2_train_step_matches_reference_in_fp32_bf16x3(cuda, lib):
     sampled full gradients 2e-3, total norm 1e-3, the Adam-update bound)."""
     from jatts_amd.models import FastSpeech2
     from jatts_amd.models.fastspeech2_train import criterion
-    from jatts_amd.training import FastSpeech2Trainer, precision_convs
+    from jatts_amd.autograd import arithmetic
+    from jatts_amd.training import FastSpeech2Trainer
     z, zi, keys, cfg = _fs2_golden()
     m = FastSpeech2(idim=20, **{**FS2_SMALL, **cfg})
     sd0 = golden_state(keys, 0)
@@ -198,7 +199,7 @@ def test_fastspeech2_train_step_matches_reference_in_fp32_bf16x3(cuda, lib):
     il, ol = batch["ilens"], batch["olens"]
     tr = FastSpeech2Trainer(m, lr=0.0008, grad_norm=1.0, warmup_steps=4000, precision="fp32_bf16x3")
     m.train()
-    with precision_convs("fp32_bf16x3"):
+    with arithmetic("fp32_bf16x3"):
         ret = m(batch["xs"], il, batch["ys"], ol, batch["durations"], il, batch["pitch"], il, batch["energys"], il)
         for k in ("before_outs", "after_outs", "d_outs", "p_outs", "e_outs"):
             assert relerr(ret[k].detach(), z["ref_" + k]) <= 2e-5, (k, relerr(ret[k].detach(), z["ref_" + k]))
@@ -256,7 +257,8 @@ def test_matcha_tts1_train_step_matches_reference_in_fp32_bf16x3(cuda, lib):
     from jatts_amd.models import MatchaTTS
     from jatts_amd.models.matchatts_train import criterion
     from jatts_amd.synthetic import matcha_golden_tweaks
-    from jatts_amd.training import MatchaTTSTrainer, precision_convs
+    from jatts_amd.autograd import arithmetic
+    from jatts_amd.training import MatchaTTSTrainer
     z, keys = load_golden("matcha_tts1_train_small.npz")
     zi, _ = load_golden("matcha_tts1_forward_small.npz")
     m = MatchaTTS(idim=20, **json.loads(str(z["config"])))
@@ -265,7 +267,7 @@ def test_matcha_tts1_train_step_matches_reference_in_fp32_bf16x3(cuda, lib):
     assert MatchaTTSTrainer(m, precision="fp32_bf16x3").precision == "fp32_bf16x3"
     t = lambda k: torch.tensor(zi[k])  # noqa: E731
     il, ol = t("text_lengths"), t("feats_lengths")
-    with precision_convs("fp32_bf16x3"):
+    with arithmetic("fp32_bf16x3"):
         ret = m(t("text"), il, t("feats"), ol, t("durations"), il, cfm_t=t("t"), cfm_noise=t("z"))
         assert relerr(ret["d_outs"].detach(), z["ref_d_outs"]) <= 2e-5
         losses = criterion(ret, t("durations"), il)
@@ -280,7 +282,8 @@ def test_matcha_mas_train_step_matches_reference_in_fp32_bf16x3(cuda, lib):
     from jatts_amd.models import MatchaTTS_MAS
     from jatts_amd.models.matchatts_train import criterion
     from jatts_amd.synthetic import matcha_golden_tweaks
-    from jatts_amd.training import MatchaTTSTrainer, precision_convs
+    from jatts_amd.autograd import arithmetic
+    from jatts_amd.training import MatchaTTSTrainer
     z, keys = load_golden("matcha_mas_train_small.npz")
     zi, _ = load_golden("matcha_forward_small.npz")
     m = MatchaTTS_MAS(idim=20, **json.loads(str(z["config"])))
@@ -289,7 +292,7 @@ def test_matcha_mas_train_step_matches_reference_in_fp32_bf16x3(cuda, lib):
     assert MatchaTTSTrainer(m, precision="fp32_bf16x3").precision == "fp32_bf16x3"
     t = lambda k: torch.tensor(zi[k])  # noqa: E731
     il, ol = t("text_lengths"), t("feats_lengths")
-    with precision_convs("fp32_bf16x3"):
+    with arithmetic("fp32_bf16x3"):
         ret = m(t("text"), il, t("feats"), ol, cfm_t=t("t"), cfm_noise=t("z"))
         assert torch.equal(ret["ds"].cpu(), torch.tensor(z["ref_ds"]))
         losses = criterion(ret, None, il, duration_loss=True, olens=ol, forward_sum=True, bin_loss=True, lambda_align=2.0)
@@ -303,7 +306,8 @@ def test_vits_train_step_matches_reference_in_fp32_bf16x3(cuda, lib):
     """test_vits_train_step_matches_reference under the emulated conv mode: same fixture, same tolerances."""
     from jatts_amd.models import VITS
     from jatts_amd.models.vits_train import criterion
-    from jatts_amd.training import VITSTrainer, precision_convs
+    from jatts_amd.autograd import arithmetic
+    from jatts_amd.training import VITSTrainer
     z, keys = load_golden("vits_train_small.npz")
     zi, _ = load_golden("vits_forward_small.npz")
     m = VITS(idim=20, **json.loads(str(z["config"])))
@@ -312,7 +316,7 @@ def test_vits_train_step_matches_reference_in_fp32_bf16x3(cuda, lib):
     assert VITSTrainer(m, precision="fp32_bf16x3").precision == "fp32_bf16x3"
     t = lambda k: torch.tensor(zi[k])  # noqa: E731
     il, ol = t("text_lengths"), t("feats_lengths")
-    with precision_convs("fp32_bf16x3"):
+    with arithmetic("fp32_bf16x3"):
         ret = m(t("text"), il, t("feats"), ol, spembs=t("spembs"), post_noise=t("noise"))
         assert torch.equal(ret["ds"].cpu(), torch.tensor(z["ref_ds"]))
         losses = criterion(ret, il, ol, duration_loss=True, forward_sum=True, bin_loss=True, lambda_align=2.0)

@@ -17,7 +17,7 @@ def test_fastspeech2_losses_match_reference(cuda, lib):
     """forward() + criterion = `_train_step` up to gen_loss (trainers/fastspeech2.py:44-84), against the reference's own
     MelLoss / DurationPredictorLoss / PitchLoss / EnergyLoss evaluated on the reference's forward() (fs2_losses_small.npz)."""
     from jatts_amd.models import FastSpeech2
-    from jatts_amd.training import fastspeech2_losses
+    from jatts_amd.models.fastspeech2_train import criterion
     z, keys = load_golden("fs2_forward_small.npz")
     ref = np.load(__import__("os").path.join(__import__("helpers").GOLDEN, "fs2_losses_small.npz"))
     m = FastSpeech2(idim=20, **FS2_SMALL)
@@ -26,7 +26,8 @@ def test_fastspeech2_losses_match_reference(cuda, lib):
     t = lambda k: torch.tensor(z[k])  # noqa: E731
     il, ol = t("text_lengths"), t("feats_lengths")
     r = m(t("text"), il, t("feats"), ol, t("durations"), il, t("pitch"), il, t("energy"), il)
-    got = fastspeech2_losses(r, t("durations"), t("pitch"), t("energy"), il)
+    with torch.no_grad():
+        got = criterion(r, t("durations"), t("pitch"), t("energy"), il)
     for k in ("mel_loss", "duration_loss", "pitch_loss", "energy_loss"):
         assert abs(float(got[k]) - float(ref[k])) <= 2e-4 * max(1.0, abs(float(ref[k]))), (k, float(got[k]), float(ref[k]))
     assert abs(float(got["loss"]) - sum(float(ref[k]) for k in ref.files)) <= 1e-3
@@ -36,7 +37,7 @@ def test_fastspeech2_losses_match_reference(cuda, lib):
                                                    (48, 20, 7, 3, [64, 30]), (192, 320, 5, 1, [300, 257, 64, 1]), (384, 200, 3, 1, [768, 500])])
 def test_conv1d_backward_matches_autograd(cuda, lib, c_in, n_out, k, dil, lens):
     from jatts_amd import hip
-    from jatts_amd.training import Conv1dFunction
+    from jatts_amd.autograd import Conv1dFunction
     g = torch.Generator().manual_seed(c_in + n_out + k)
     R = sum(lens)
     x = torch.randn(R, c_in, generator=g)
@@ -66,7 +67,7 @@ def test_one_optimiser_step_through_the_hip_conv(cuda, lib):
     """A two-layer ragged conv net trained for a few Adam steps on the HIP forward / backward: the loss goes down and the
     parameters follow the same trajectory as the torch reference model to f32 accuracy."""
     from jatts_amd import hip
-    from jatts_amd.training import RaggedConv1d
+    from jatts_amd.autograd import RaggedConv1d
     torch.manual_seed(0)
     lens = [50, 23, 64]
     rb = hip.RaggedBatch(lens, cuda)
@@ -134,17 +135,16 @@ def test_fastspeech2_train_step_matches_reference(cuda, lib, precision):
     tr = FastSpeech2Trainer(m, lr=0.0008, grad_norm=1.0, warmup_steps=4000, precision=precision)
     # forward + backward only first (gradients are consumed by the step)
     m.train()
-    from jatts_amd import training as _tr
+    from jatts_amd.autograd import arithmetic
     from jatts_amd.models.fastspeech2_train import criterion
-    _tr.SPLIT_CONVS[0] = precision == "fp32_split"          # (what the trainer sets around its own steps; reset at the end of the manual part)
-    ret = m(batch["xs"], il, batch["ys"], ol, batch["durations"], il, batch["pitch"], il, batch["energys"], il)
-    for k in ("before_outs", "after_outs", "d_outs", "p_outs", "e_outs"):
-        assert relerr(ret[k].detach(), z["ref_" + k]) <= 2e-5, (k, relerr(ret[k].detach(), z["ref_" + k]))
-    losses = criterion(ret, batch["durations"], batch["pitch"], batch["energys"], il)
-    for k in ("mel_loss", "duration_loss", "pitch_loss", "energy_loss"):
-        assert abs(float(losses[k]) - float(z[k])) <= 2e-5 * max(1.0, abs(float(z[k]))), (k, float(losses[k]), float(z[k]))
-    losses["loss"].backward()
-    _tr.SPLIT_CONVS[0] = False
+    with arithmetic(precision):          # (what the trainer sets around its own steps)
+        ret = m(batch["xs"], il, batch["ys"], ol, batch["durations"], il, batch["pitch"], il, batch["energys"], il)
+        for k in ("before_outs", "after_outs", "d_outs", "p_outs", "e_outs"):
+            assert relerr(ret[k].detach(), z["ref_" + k]) <= 2e-5, (k, relerr(ret[k].detach(), z["ref_" + k]))
+        losses = criterion(ret, batch["durations"], batch["pitch"], batch["energys"], il)
+        for k in ("mel_loss", "duration_loss", "pitch_loss", "energy_loss"):
+            assert abs(float(losses[k]) - float(z[k])) <= 2e-5 * max(1.0, abs(float(z[k]))), (k, float(losses[k]), float(z[k]))
+        losses["loss"].backward()
     names = json.loads(str(z["grad_names"]))
     P = dict(m.named_parameters())
     worst = ("", 0.0)
