@@ -898,7 +898,9 @@ int jatts_alignment_logp(const jatts_ragged* rg_feats, const int32_t* cu_text, i
 
 /* Gradient of jatts_alignment_logp (modules/alignments.py:50-60 under autograd), same geometry, all f32, two fixed-order passes without atomics:
  * g = dlog_p at the utterance's own tokens (0 elsewhere), dscore = g - exp(log_p) sum_j g, the squared distance recomputed by direct differences
- * (exp(log_p) is re-evaluated from those distances, more accurately summed than the forward's; the saved log_p only marks -inf columns),
+ * (exp(log_p) is re-evaluated from those distances, more accurately summed than the forward's; the saved log_p only marks -inf columns: a column
+ * the caller masked to -inf has probability 0 and dscore 0, so its w is an exact zero, as masked_fill(-inf) before the log-softmax gives under
+ * autograd; its dlog_p still counts in sum_j g),
  * w = -dscore / sqrt(max(d^2, 1e-24)) -> the workspace w f32 [frame rows][ld];  d_feats[i] = sum_j w_ij (f_i - t_j) f32 [frame rows][adim];
  * d_text[j] = sum_i w_ij (t_j - f_i) f32 [token rows][adim] (the valid-packed token rows of cu_text).  log_p: the forward's output, row pitch ld;
  * dlog_p: row pitch ld_g; both >= max_text_len.  max_text_len <= 492: the token tile (65 floats a token), the frame tile and the 16 x T weights

@@ -602,7 +602,9 @@ class AlignLogProb(torch.autograd.Function):
     forward: jatts_alignment_logp.  backward, by MAS_OWN_KERNELS["align_bwd"]: True = jatts_alignment_logp_bwd -- the log-softmax backward, then with
     w = -d_score / dist (the distance recomputed by direct differences, as the forward kernel does), d_ff_i = sum_j w_ij (f_i - t_j) and
     d_tf_j = sum_i w_ij (t_j - f_i): f32, two fixed-order passes, no atomics; the token gradient is scattered back to the padded rows (zeros at padded
-    tokens; the kernel masks by `ilens`, which is what `valid` is built from).  False = the round-10 form, float64 torch ops and three torch.matmul calls."""
+    tokens; the kernel masks by `ilens`, which is what `valid` is built from).  False = the round-10 form, float64 torch ops and three torch.matmul calls.
+    One contract for both: a column whose saved log_p is -inf has probability 0 and w = 0 (masked_fill(-inf) passes nothing back); dlp of the padding
+    is ignored, dlp of a -inf column inside the valid tokens still counts in sum_j g, as under autograd."""
 
     @staticmethod
     def forward(ctx, ff, tf, B, ilens, tsel=None, valid=None):
@@ -646,7 +648,8 @@ class AlignLogProb(torch.autograd.Function):
         dscore = g - torch.exp(lp.double()) * g.sum(-1, keepdim=True)
         F_, T_ = ff.view(B, To, A_).double(), tf.view(B, Tm, A_).double()
         d2 = (F_ * F_).sum(-1).unsqueeze(2) + (T_ * T_).sum(-1).unsqueeze(1) - 2.0 * torch.matmul(F_, T_.transpose(1, 2))
-        w = (-dscore / torch.sqrt(d2.clamp_min(1e-24))).masked_fill(~vm, 0.0)
+        # a -inf column of the saved lp (the padding; a column a caller masked inside the valid tokens) passes no gradient back, as in the kernel: w = 0
+        w = (-dscore / torch.sqrt(d2.clamp_min(1e-24))).masked_fill(~torch.isfinite(lp), 0.0)
         dF = w.sum(-1, keepdim=True) * F_ - torch.matmul(w, T_)
         # sum_i w_ij rides along as one more GEMM column: torch's strided multi-block reduction keeps its block semaphores zero with a
         # memset, which did not replay reliably inside a captured step on this stack (garbage text-side gradients at B 32 x 768 frames)

@@ -9,6 +9,8 @@ namespace {
 
 constexpr int MAS_SLOTS = 4;    // tokens per thread: T_inp <= 1024
 constexpr int MAS_PF = 8;       // log-prob columns prefetched ahead (registers)
+constexpr int MAS_RED = 4;      // mas_kernel's static LDS: one float64 partial per wave (block_sum_f64).  It comes off the 160 KiB the dynamic part may use
+constexpr size_t MAS_LDS_MAX = 160 * 1024 - MAS_RED * sizeof(double);
 
 __device__ __forceinline__ double block_sum_f64(double v, double* red) {
 #pragma unroll
@@ -37,7 +39,7 @@ __global__ __launch_bounds__(256) void mas_kernel(jatts_ragged rg_f, const int32
   double* qbuf = reinterpret_cast<double*>(dec + (size_t)T_mel * W);                  // [2][T_inp + 1]
   int* cnt = reinterpret_cast<int*>(qbuf + 2 * (T_inp + 1));                          // [T_inp]
   int* pth = cnt + T_inp;                                                              // [T_mel]
-  __shared__ double red[4];
+  __shared__ double red[MAS_RED];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* lp = logp + (int64_t)row0 * ld;
   const double NEG = -INFINITY;
@@ -254,7 +256,8 @@ __global__ __launch_bounds__(256) void align_logp_bwd_frames_kernel(jatts_ragged
     const float* gr = dlogp + (int64_t)(row0 + f0 + f) * ldg;
     const float* lr = logp + (int64_t)(row0 + f0 + f) * ld;
     float gs = 0.f, mx = -INFINITY;
-    // (a column whose saved log_p is -inf was masked by the caller: it is left out of the softmax as it was in the forward, its probability is 0)
+    // (a column whose saved log_p is -inf was masked by the caller: it is left out of the softmax as it was in the forward, its probability is 0.
+    // Its dlog_p still counts in sum_j g, as it does in the log-softmax backward of masked_fill(-inf) under autograd; its own dscore is 0, below)
     for (int i = lane; i < T_t; i += 64) { gs += gr[i]; if (isfinite(lr[i])) mx = fmaxf(mx, -sqrtf(sc[i * AL_FB + f])); }
     gs = wave_sum(gs);
     mx = wave_max(mx);
@@ -266,8 +269,8 @@ __global__ __launch_bounds__(256) void align_logp_bwd_frames_kernel(jatts_ragged
       float w = 0.f;
       if (i < T_t) {
         const float d2 = sc[i * AL_FB + f];
-        const float prob = isfinite(lr[i]) ? expf(-sqrtf(d2) - lse) : 0.f;      // (a column the caller masked to -inf stays at probability 0)
-        const float dscore = gr[i] - prob * gs;
+        const bool on = isfinite(lr[i]);      // (a column the caller masked to -inf: probability 0, and masked_fill passes no gradient back: dscore 0)
+        const float dscore = on ? gr[i] - expf(-sqrtf(d2) - lse) * gs : 0.f;
         w = -dscore / sqrtf(fmaxf(d2, 1e-24f));
         sc[i * AL_FB + f] = w;
       }
@@ -373,7 +376,7 @@ extern "C" int jatts_mas_viterbi(const jatts_ragged* rg_feats, const int32_t* cu
     return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "mas_viterbi: text length must be 1..1024 and <= ld");
   const size_t W = (max_text_len + 63) / 64;
   const size_t lds = (size_t)rg_feats->max_len * W * 8 + 2 * (size_t)(max_text_len + 1) * 8 + (size_t)max_text_len * 4 + (size_t)rg_feats->max_len * 4 + 16;
-  if (lds > 160 * 1024) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "mas_viterbi: T_feats x T_text decision bits exceed 160 KiB of LDS");
+  if (lds > MAS_LDS_MAX) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "mas_viterbi: T_feats x T_text decision bits exceed 160 KiB of LDS");
   JATTS_RAISE_LDS_LIMIT(mas_kernel);
   hipLaunchKernelGGL(mas_kernel, dim3((unsigned)rg_feats->n_seq), dim3(256), lds, (hipStream_t)stream, *rg_feats, cu_text, log_p, ld, path, dur, score);
   JATTS_CHECK_LAUNCH();
