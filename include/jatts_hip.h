@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define JATTS_ABI_VERSION 7   /* (round 29 added jatts_frame_select, jatts_gather_rows, jatts_pairwise_dist, jatts_dtw, jatts_dtw_path_stats and jatts_dtw_max_rows without a bump, as round 15 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 27 appended tap_group_n / tap_a0 / tap_b0 / tap_k to jatts_conv_desc WITHOUT a bump: the fields are a hint that every kernel may ignore, so a library from before them, which never reads that far, computes the same values; tests/test_attn_precision_cpu.py pins 7 -- a caller built against an older header must not be paired with this library: it would read the hint beyond the caller's struct) (round 15 added jatts_stft_mag, jatts_logmel_post, jatts_energy_frames, jatts_energy_adjust and jatts_token_average without a bump, as rounds 10, 11 and 13 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 13: jatts_hifigan_resunit / jatts_resunit_variant take w2 == NULL as the single-conv dilation unit, without a bump: no descriptor or signature changed, and a library from before it lacks jatts_resunit_single_conv, so it is refused when _abi.load binds that symbol) (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
+#define JATTS_ABI_VERSION 8   /* 8: the deterministic reductions take their scratch as an argument -- jatts_scratch, `const jatts_scratch* scratch` in front of `stream` in thirteen entry points, and the process-wide registration call is gone; (round 29 added jatts_frame_select, jatts_gather_rows, jatts_pairwise_dist, jatts_dtw, jatts_dtw_path_stats and jatts_dtw_max_rows without a bump, as round 15 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 27 appended tap_group_n / tap_a0 / tap_b0 / tap_k to jatts_conv_desc WITHOUT a bump: the fields are a hint that every kernel may ignore, so a library from before them, which never reads that far, computes the same values; tests/test_attn_precision_cpu.py pins the number -- a caller built against an older header must not be paired with this library: it would read the hint beyond the caller's struct) (round 15 added jatts_stft_mag, jatts_logmel_post, jatts_energy_frames, jatts_energy_adjust and jatts_token_average without a bump, as rounds 10, 11 and 13 did: no descriptor or existing signature changed, and a library without the symbols is refused when _abi.load binds them) (round 13: jatts_hifigan_resunit / jatts_resunit_variant take w2 == NULL as the single-conv dilation unit, without a bump: no descriptor or signature changed, and a library from before it lacks jatts_resunit_single_conv, so it is refused when _abi.load binds that symbol) (round 10 added jatts_bgemm_emul without a bump: no descriptor or existing signature changed, and a library without the symbol is refused when _abi.load binds it) 7 (round 8): jatts_relpos_attention takes JATTS_F32E (no descriptor change; a version-6 library answers it "unknown dtype"); 6 (round 7): + jatts_pack_conv_weight_bf16x3, jatts_conv1d_wgrad_emul (training on JATTS_F32E); 5: jatts_resunit_desc + variant (appended), jatts_resunit_variant; 4 (round 6): + jatts_mfma_probe / jatts_mfma_probe_flops, jatts_conv_desc + n_split / ldy2 / y2 / y2_seq_col0 / w_layout and jatts_resunit_desc + w_layout (appended), jatts_unit_weight_index_k32; 3 (round 5): jatts_ragged + total_rows AND host_lens -- the struct grew from 24 to 32 bytes,
                                 * so every descriptor that embeds it (jatts_conv_desc, jatts_resunit_desc, jatts_resblock_desc, jatts_relattn_desc) shifted by 8 bytes; JATTS_F32E; 2 (round 4): jatts_conv_desc + w_inv / act_a / act_b, jatts_resunit_desc + ws1 / ws2, jatts_resblock_desc + ws1 / ws2;
                                 * bumped whenever a descriptor's layout or an entry point's signature changes: a stale library is refused at load */
 
@@ -94,6 +94,24 @@ typedef struct jatts_ragged {
                              * inside descriptors copied to the device as kernel arguments: DEVICE CODE MUST NEVER DEREFERENCE IT -- kernels only
                              * compare it with NULL (common.h: ragged_is_1d) to learn which grid form they were launched with. */
 } jatts_ragged;
+
+/* Scratch of the DETERMINISTIC reductions: jatts_layernorm_bwd, jatts_groupnorm_bwd, jatts_snakebeta_bwd, jatts_dwconv_wgrad,
+ * jatts_col_stats, jatts_col_sum, jatts_col_wsum, jatts_seq_sum, jatts_qkv_split_bwd, jatts_sumsq, the VALU path of jatts_conv1d_wgrad
+ * (and of jatts_conv1d_wgrad_emul, which falls through to it) and the energy sum of jatts_stft_mag reduce across workgroups through
+ * per-workgroup slabs that the last-arriving workgroup adds up in a fixed order (no f32 atomics: results are bit-identical from run to
+ * run, like the reference's).  Each of them takes the scratch as its argument in front of `stream`.
+ * buf: device memory, 16-byte aligned, ZERO-filled by the caller once, owned by the caller and alive until the last launch that was
+ * given it has run (a captured graph bakes its address in); the first 64 KiB hold tickets, the rest slabs.  Every launch leaves the
+ * tickets zero again, so one scratch serves any number of launches -- but launches that share a scratch must be STREAM-ORDERED: the
+ * same stream, or an event between them (jatts_amd.hip keeps one scratch per device and makes a stream other than its last user wait).
+ * Independent streams take independent scratches.
+ * Where a call reduces, a NULL scratch, a NULL or misaligned buf, more tickets than the 16384 of the head, or too few bytes are refused
+ * with JATTS_ERR_ARG before anything is launched (the message names the bytes of slabs the launch needs; + 64 KiB of tickets).
+ * scratch may be NULL where a call does not reduce through it; each function says where that is. */
+typedef struct jatts_scratch {
+  void* buf;
+  int64_t bytes;
+} jatts_scratch;
 
 /* ---------------------------------------------------------------------------------
  * Conv1d / Linear as MFMA implicit GEMM.
@@ -297,11 +315,14 @@ int jatts_masked_loss(const jatts_ragged* rg, const float* a, int32_t lda, const
  * 0 <= pad <= (k_w - 1) * dil as for jatts_conv1d (JATTS_ERR_ARG otherwise; jatts_conv1d_wgrad_emul alike); rg->len_mul scales every sequence as there.
  * workspace != NULL (n_seq * (k_w * pad64(n_out) * pad64(c_in) + pad64(n_out)) floats): split-K partials are written there and summed
  * by a second launch, dw is OVERWRITTEN (deterministic, no atomics).  workspace == NULL: refused on the MFMA path (k_w 1 / 3 / 5); the VALU
- * path (other widths) then ACCUMULATES into dw, through the fixed-order slabs of jatts_set_workspace (round 4: no f32 atomics anywhere).
+ * path (other widths) then ACCUMULATES into dw.
  * db (nullable, n_out floats, OVERWRITTEN): the bias gradient sum_t dy[t][n] of the same convolution (torch.nn.Conv1d's bias.grad).  On
- * the MFMA path it falls out of the dy tiles the kernel stages anyway (no second pass over dy); otherwise a fixed-order column-sum launch. */
+ * the MFMA path it falls out of the dy tiles the kernel stages anyway (no second pass over dy); otherwise a fixed-order column-sum launch.
+ * scratch (jatts_scratch): the VALU path reduces dw, and db, through its fixed-order slabs (round 4: no f32 atomics anywhere); the MFMA
+ * path never touches it and takes NULL. */
 int jatts_conv1d_wgrad(const jatts_ragged* rg, const float* x, int32_t ldx, const float* dy, int32_t ldy, int32_t c_in,
-                       int32_t n_out, int32_t k_w, int32_t dil, int32_t pad, float* dw, float* db, float* workspace, void* stream);
+                       int32_t n_out, int32_t k_w, int32_t dil, int32_t pad, float* dw, float* db, float* workspace,
+                       const jatts_scratch* scratch, void* stream);
 /* Pack a torch-layout f32 weight (n_out, c_in, k_w) into jatts_conv1d's fragment order (zero padded: n to 32, c to c_mult) as
  * `dtype`, in one launch.  mode 0: the weight itself; mode 1: the data-gradient operand W'[c][n][k'] = W[n][c][k_w-1-k'] (a conv from
  * n_out to c_in channels; padded sizes follow the swapped roles).  out: k_w * pad32(n) * pad(c, c_mult) elements. */
@@ -323,21 +344,25 @@ int jatts_pack_conv_weight_bf16x3(const float* w, int32_t n_out, int32_t c_in, i
  * v_mfma_f32_16x16x32_bf16, leading and small products in separate accumulators joined by one add per workgroup (a one-term sum is within
  * 2.01 x 2^-24 of dy x); JATTS_F32E6 is refused.  k_w 1 / 3 / 5 with (k_w - 1) dil <= 32; any other geometry returns through the exact-f32 entry.
  * Same arguments and workspace contract as jatts_conv1d_wgrad (workspace required, dw and db OVERWRITTEN, fixed-order split-K: two runs are
- * bit-identical); db is summed in exact f32 from the staged dy tiles. */
+ * bit-identical); db is summed in exact f32 from the staged dy tiles.  scratch: handed on to the exact-f32 entry, unused otherwise. */
 int jatts_conv1d_wgrad_emul(const jatts_ragged* rg, const float* x, int32_t ldx, const float* dy, int32_t ldy, int32_t c_in, int32_t n_out, int32_t k_w,
-                            int32_t dil, int32_t pad, int32_t dtype, float* dw, float* db, float* workspace, void* stream);
+                            int32_t dil, int32_t pad, int32_t dtype, float* dw, float* db, float* workspace, const jatts_scratch* scratch,
+                            void* stream);
 /* out[c] += sum over rows of x[row][c] (bias gradient; caller zeroes out). */
-int jatts_col_sum(const float* x, int32_t ld, int64_t rows, int32_t dim, float* out, void* stream);
+int jatts_col_sum(const float* x, int32_t ld, int64_t rows, int32_t dim, float* out, const jatts_scratch* scratch, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Training side, second slice of SURVEY 8 f.4: the backward passes (and train-mode forward pieces) of the FastSpeech2 layers
- * around the conv op.  All f32, [rows][dim] row-major; every "+=" output is accumulated with f32 atomics (caller zeroes).
+ * around the conv op.  All f32, [rows][dim] row-major; "+=" outputs are accumulated in a fixed order, never with f32 atomics (the
+ * caller zeroes them); those that sum across workgroups do it through the caller's jatts_scratch, the argument in front of `stream`.
+ * An empty launch (no rows) returns JATTS_OK before it looks at the scratch.
  * The reference has no interface for these: they stand where torch autograd runs for the jatts/modules layers under
  * jatts/trainers/fastspeech2.py:86-96 (gen_loss.backward(); clip_grad_norm_; optimizer.step()).
  * ------------------------------------------------------------------------------- */
-/* LayerNorm over the channels (modules/transformer/layer_norm.py:12-42): dx (nullable), dgamma += , dbeta += (both or neither). dim <= 1536. */
+/* LayerNorm over the channels (modules/transformer/layer_norm.py:12-42): dx (nullable), dgamma += , dbeta += (both or neither;
+ * without them scratch may be NULL). dim <= 1536. */
 int jatts_layernorm_bwd(const float* x, int32_t ldx, const float* dy, int32_t lddy, const float* gamma, int64_t rows, int32_t dim,
-                        float eps, float* dx, int32_t lddx, float* dgamma, float* dbeta, void* stream);
+                        float eps, float* dx, int32_t lddx, float* dgamma, float* dbeta, const jatts_scratch* scratch, void* stream);
 /* Element-wise activations, mode 1 ReLU, 2 tanh, 3 Swish (x sigmoid x, modules/conformer/swish.py), 4 Mish; bwd: dx = dy * act'(x). */
 int jatts_act_fwd(int32_t mode, const float* x, float* y, int64_t n, void* stream);
 int jatts_act_bwd(int32_t mode, const float* x, const float* dy, float* dx, int64_t n, void* stream);
@@ -350,12 +375,12 @@ int jatts_dwconv(const jatts_ragged* rg, const float* x, const float* w, const f
                  int32_t pad, int32_t flip, void* stream);
 /* dw[c][k] += sum_t dy[t][c] x[t + k - pad][c]. */
 int jatts_dwconv_wgrad(const jatts_ragged* rg, const float* x, const float* dy, float* dw, int32_t dim, int32_t k_w, int32_t pad,
-                       void* stream);
+                       const jatts_scratch* scratch, void* stream);
 /* Column sums for batch-statistics BatchNorm1d (train mode of convolution.py:53 / pre_postnets.py:112-143):
  * mode 0: out0[c] += sum_r (x - shift[c]), out1[c] += sum_r (x - shift[c])^2 (shift nullable);
  * mode 1: out0[c] += sum_r y2, out1[c] += sum_r y2 * (x - shift[c]) * mul[c]   (y2 = dy, shift = mean, mul = rstd). */
 int jatts_col_stats(const float* x, const float* y2, int32_t ld, int64_t rows, int32_t dim, const float* shift, const float* mul,
-                    int32_t mode, float* out0, float* out1, void* stream);
+                    int32_t mode, float* out0, float* out1, const jatts_scratch* scratch, void* stream);
 /* dx = gamma rstd (dy - s_dy / rows - xhat s_dyx / rows), xhat = (x - mean) rstd. */
 int jatts_bn_bwd_apply(const float* x, const float* dy, int64_t rows, int32_t dim, const float* mean, const float* rstd,
                        const float* gamma, const float* s_dy, const float* s_dyx, float* dx, void* stream);
@@ -390,7 +415,7 @@ int jatts_concat2(const float* a, const float* b, int64_t rows, int32_t dim, flo
  * out[r][c] (+)= v[r] w[c] + bias[c];  out[c] += sum_r v[r] x[r][c];  y[r] = bias[0] + sum_c x[r][c] w[c]. */
 int jatts_outer_rows(const float* v, const float* w, const float* bias, int64_t rows, int32_t dim, int32_t accumulate, float* out,
                      void* stream);
-int jatts_col_wsum(const float* x, int32_t ld, const float* v, int64_t rows, int32_t dim, float* out, void* stream);
+int jatts_col_wsum(const float* x, int32_t ld, const float* v, int64_t rows, int32_t dim, float* out, const jatts_scratch* scratch, void* stream);
 int jatts_row_dot(const float* x, int32_t ld, const float* w, const float* bias, int64_t rows, int32_t dim, float* y, void* stream);
 /* Gradient of jatts_masked_loss w.r.t. a: da = *upstream (NULL: 1) * scale * {sign(a - b'), 2 (a - b')} on valid rows, 0 elsewhere. */
 int jatts_masked_loss_bwd(const jatts_ragged* rg, const float* a, int32_t lda, const float* b, int32_t ldb, int32_t dim,
@@ -398,17 +423,18 @@ int jatts_masked_loss_bwd(const jatts_ragged* rg, const float* a, int32_t lda, c
                           int32_t ldda, void* stream);
 /* torch.nn.GroupNorm(groups, dim) over each sequence's [rows][dim / groups] slabs (matchatts/decoder.py:66-78 Block1D; the
  * statistics run over every row of the sequence as laid out, i.e. the padded length of a padded batch).  fwd also returns the
- * per-(sequence, group) mean / rstd [n_seq * groups] for the backward; bwd: dx (nullable), dgamma +=, dbeta += (both or neither).
- * dim / groups must divide 256. */
+ * per-(sequence, group) mean / rstd [n_seq * groups] for the backward; bwd: dx (nullable), dgamma +=, dbeta += (both or neither; without
+ * them scratch may be NULL).  dim / groups must divide 256. */
 int jatts_groupnorm_fwd(const jatts_ragged* rg, const float* x, int32_t dim, int32_t groups, const float* gamma, const float* beta,
                         float eps, float* y, float* mean, float* rstd, void* stream);
 int jatts_groupnorm_bwd(const jatts_ragged* rg, const float* x, const float* dy, int32_t dim, int32_t groups, const float* gamma,
-                        const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta, void* stream);
+                        const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta, const jatts_scratch* scratch,
+                        void* stream);
 /* SnakeBeta with log-scale parameters (matchatts/transformer.py:84-102): y = x + sin^2(exp(alpha) x) / (exp(beta) + 1e-9);
  * bwd: dx, dalpha +=, dbeta += (gradients w.r.t. the LOG parameters, as stored). */
 int jatts_snakebeta_fwd(const float* x, float* y, int64_t rows, int32_t dim, const float* alpha, const float* beta, void* stream);
 int jatts_snakebeta_bwd(const float* x, const float* dy, int64_t rows, int32_t dim, const float* alpha, const float* beta, float* dx,
-                        float* dalpha, float* dbeta, void* stream);
+                        float* dalpha, float* dbeta, const jatts_scratch* scratch, void* stream);
 /* ForwardSumLoss of the alignment framework (losses/forward_sum_loss.py:41-78): per utterance b, F.ctc_loss(reduction "mean",
  * zero_infinity) on log_p[b][t][j] (t < olens[b], j < ilens[b]; the caller has already added the beta-binomial prior) with a
  * constant blank column log_blank and targets 1..ilens[b].  nll[b] = -log p / ilens[b] (0 when impossible).  grad (nullable,
@@ -416,21 +442,22 @@ int jatts_snakebeta_bwd(const float* x, const float* dy, int64_t rows, int32_t d
  * (2 * max_ilen + 1) floats. */
 int jatts_ctc_forward_sum(const float* log_p, int32_t n_batch, int32_t t_max, int32_t ld, const int32_t* ilens, const int32_t* olens,
                           int32_t max_ilen, float log_blank, float* workspace, float* nll, float* grad, float grad_scale, void* stream);
-/* out[s][c] += sum over the rows of sequence s of x[row][c] (f32 atomics; caller zeroes out [n_seq][dim]): the gradient of a
+/* out[s][c] += sum over the rows of sequence s of x[row][c] (fixed order; caller zeroes out [n_seq][dim]): the gradient of a
  * per-sequence vector added to every row (speaker / time embeddings, WaveNet global conditioning). */
-int jatts_seq_sum(const jatts_ragged* rg, const float* x, int32_t dim, float* out, void* stream);
+int jatts_seq_sum(const jatts_ragged* rg, const float* x, int32_t dim, float* out, const jatts_scratch* scratch, void* stream);
 /* Inverted dropout with a counter-based mask: y[i] = keep(seed, i) ? x[i] / (1 - p) : 0; the backward is the same call on dy. */
 /* seed_dev (may be NULL): the mask seed is *seed_dev + seed -- a captured graph replays with a new base seed per step (device memory) and
  * `seed` as the call site's offset. */
 int jatts_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, const uint64_t* seed_dev, void* stream);
 /* Head split of the fused Q|K|V projection for the training-time attention (modules/transformer/attention.py:81-88,190-195):
  * qkv [n_batch t_len][3 A] (A = n_heads d_k) -> qu = q + pos_bias_u, qv = q + pos_bias_v, k, vv, each [n_batch][n_heads][t_len][d_k]
- * contiguous.  _bwd: the four gradients -> dqkv [rows][3 A] (overwritten) and du / dv [A] += column sums (caller zeroes them).
+ * contiguous.  _bwd: the four gradients -> dqkv [rows][3 A] (overwritten) and du / dv [A] += column sums (caller zeroes them; with
+ * both NULL scratch may be NULL).
  * u == v == NULL (with qv / dqv / du / dv NULL): the plain head split of an attention without position biases (matchatts/transformer.py:16-25). */
 int jatts_qkv_split(const float* qkv, const float* u, const float* v, int32_t n_batch, int32_t t_len, int32_t n_heads, int32_t d_k, float* qu,
                     float* qv, float* k, float* vv, void* stream);
 int jatts_qkv_split_bwd(const float* dqu, const float* dqv, const float* dk, const float* dvv, int32_t n_batch, int32_t t_len, int32_t n_heads,
-                        int32_t d_k, float* dqkv, float* du, float* dv, void* stream);
+                        int32_t d_k, float* dqkv, float* du, float* dv, const jatts_scratch* scratch, void* stream);
 /* dropout(act(x)) in one pass (the FFN's ReLU -> Dropout, modules/transformer/multi_layer_conv.py:52-63; modes as jatts_act_fwd, mask as
  * jatts_dropout: bit-identical to the two launches).  dy == NULL: out = keep ? act(x) / (1 - p) : 0; else out = keep ? dy act'(x) / (1 - p) : 0. */
 int jatts_act_dropout(int32_t mode, const float* x, const float* dy, float* out, int64_t n, float p, uint64_t seed, const uint64_t* seed_dev,
@@ -448,7 +475,7 @@ int jatts_gather_grads(const float* const* src, const int64_t* numel, const int6
 /* *out += sum x^2 (double); Adam step (torch.optim.Adam semantics, step counts from 1) with the gradient scaled by
  * min(1, max_norm / (sqrt(*grad_sumsq) + 1e-6)) when grad_sumsq != NULL and max_norm > 0 (clip_grad_norm_).  The hyper-parameters
  * are doubles: bias corrections and step size are computed in double (torch computes them as Python floats) and rounded once. */
-int jatts_sumsq(const float* x, int64_t n, double* out, void* stream);
+int jatts_sumsq(const float* x, int64_t n, double* out, const jatts_scratch* scratch, void* stream);
 int jatts_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                     double weight_decay, int64_t step, const double* grad_sumsq, float max_norm, const float* hyper_dev, void* stream);
 /* hyper_dev (may be NULL): 7 device floats [lr / bc1, 1 - beta1, beta2, 1 - beta2, eps, weight_decay, sqrt(bc2)] that REPLACE the host
@@ -494,17 +521,6 @@ int jatts_bgemm(const float* a, int64_t sa_outer, int64_t sa_inner, int32_t lda,
 int jatts_bgemm_emul(const float* a, int64_t sa_outer, int64_t sa_inner, int32_t lda, int32_t trans_a, const float* b, int64_t sb_outer,
                      int64_t sb_inner, int32_t ldb, int32_t trans_b, float* c, int64_t sc_outer, int64_t sc_inner, int32_t ldc, int32_t n_outer,
                      int32_t n_inner, int32_t m, int32_t n, int32_t k, float alpha, int32_t accumulate, int32_t arith, void* stream);
-
-/* Scratch of the DETERMINISTIC reductions of the training kernels (round 4): jatts_layernorm_bwd, jatts_groupnorm_bwd,
- * jatts_snakebeta_bwd, jatts_dwconv_wgrad, jatts_col_stats, jatts_col_sum, jatts_col_wsum, jatts_seq_sum, jatts_qkv_split_bwd,
- * jatts_sumsq and the VALU path / bias sums of jatts_conv1d_wgrad reduce across workgroups through per-workgroup slabs that the
- * last-arriving workgroup adds up in a fixed order (no f32 atomics: results are bit-identical from run to run, like the
- * reference's).  buf: device memory, 16-byte aligned, ZERO-filled by the caller once, owned by the caller and kept
- * alive until replaced (a captured graph bakes its address in); the first 64 KiB hold tickets, the rest slabs.  A launch that needs
- * more fails with JATTS_ERR_ARG naming the size.  Launches of one stream serialise on it; two streams must not run these kernels
- * concurrently: the scratch is process-wide (jatts_amd.hip records the stream of the last reduction launch and makes any other stream
- * wait for it with an event before its own).  buf = NULL unregisters. */
-int jatts_set_workspace(void* buf, int64_t bytes);
 
 /* Output stage: y[t] = tanh( b + sum_{tap,c} w[tap][c] * lrelu( in_scale * sum_i x_i[t+tap-pad][c] ) )
  * (HiFiGANGenerator.output_conv: LeakyReLU(0.01) -> Conv1d(C,1,k) -> Tanh).  w: f32 [k_w][c_in]. */
@@ -692,12 +708,13 @@ int jatts_se_scale_add(const jatts_ragged* rg, const float* x, int32_t dim, cons
  * zero-padded analysis window (jatts_amd.features.dft_table folds it in float64 and rounds once); padding columns are zero.
  * rg_frames: utterance b has 1 + L_b / hop frames; cu_samples (device, n_seq+1) delimits the waveforms, host_samples (HOST, n_seq)
  * repeats their lengths for the checks below (read at launch time only).  pow_sum (optional, [rows]): sum_k re^2 + im^2 per frame
- * (energy.py:86-89), summed in a fixed order through the scratch of jatts_set_workspace (n_bin_tiles * rows floats).
+ * (energy.py:86-89), summed in a fixed order through `scratch` (jatts_scratch: n_bin_tiles * rows floats of slabs; NULL without pow_sum).
  * Neither the frame matrix nor the complex spectrum is written to memory.  JATTS_ERR_ARG: n_fft > 2048 or not a multiple of 64;
  * hop < 1 or hop > n_fft; an utterance with L <= n_fft/2 (reflect would fold twice; torch.stft refuses it too); ldo < n_bins;
  * rg_frames->max_len != max_b (1 + L_b / hop). */
 int jatts_stft_mag(const jatts_ragged* rg_frames, const int32_t* cu_samples, const int32_t* host_samples, const float* x,
-                   const float* table, int32_t n_fft, int32_t hop, float* mag, int32_t ldo, float* pow_sum, void* stream);
+                   const float* table, int32_t n_fft, int32_t hop, float* mag, int32_t ldo, float* pow_sum,
+                   const jatts_scratch* scratch, void* stream);
 /* out[row][c] = log_b(max(eps, mel[row][c])) for c < n_mels, 0 up to ldo (mel.py:64-73).  log_base: 0 = natural, 2 or 10. */
 int jatts_logmel_post(const float* mel, int32_t ldm, int32_t n_mels, int64_t rows, float eps, int32_t log_base, float* out,
                       int32_t ldo, void* stream);
@@ -782,7 +799,7 @@ int32_t jatts_stats_rows_per_group(void);
  * accumulated): state <- Chan / Golub / LeVeque pairwise update of state with the batch, accumulated in float64 in ONE pass about a
  * shift (the running mean; the call's first row while the state is empty).  Fixed order: the rows are cut into groups of
  * JATTS_STATS_ROWS_PER_GROUP, one workgroup per group and column tile stores its two sums to `ws` (device, the CALLER's, at least
- * ceil(rows / JATTS_STATS_ROWS_PER_GROUP) * 2 * dim doubles, free again when the call has run; not the scratch of jatts_set_workspace), a second
+ * ceil(rows / JATTS_STATS_ROWS_PER_GROUP) * 2 * dim doubles, free again when the call has run; not a jatts_scratch), a second
  * single-workgroup launch adds the groups in order and updates the state.  No atomics, no host synchronisation: the state's bits
  * depend on the sequence of calls, their rows and dim only.  rows == 0: no-op.  NaN is NOT skipped (sklearn skips it).
  * JATTS_ERR_ARG: dim < 1, ld < dim, rows < 0, a workspace too small. */

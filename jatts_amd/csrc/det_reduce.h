@@ -3,26 +3,26 @@
 // The small parameter-gradient reductions (LayerNorm gamma / beta, bias and column sums, depthwise-conv weights, BatchNorm / GroupNorm /
 // SnakeBeta statistics, the gradient norm) used to add per-workgroup partial sums into the result with f32 atomics: the order of the
 // additions, and with it the last bits of the sum, changed from run to run.  The reference is bit-identical run to run, so is
-// this: every workgroup stores its partial vector to a SLAB in a library-wide scratch buffer, takes a ticket, and the workgroup that
-// draws the last ticket adds the slabs up in a FIXED order (slab index, then a fixed tree over its waves) and accumulates the total into
-// the result -- one launch, no atomics on data, no zero-filled accumulator required by the reduction itself.
+// this: every workgroup stores its partial vector to a SLAB in the scratch buffer the caller passes (jatts_scratch), takes a ticket, and
+// the workgroup that draws the last ticket adds the slabs up in a FIXED order (slab index, then a fixed tree over its waves) and
+// accumulates the total into the result -- one launch, no atomics on data, no zero-filled accumulator required by the reduction itself.
 //
 // Publication protocol (MI355X: 8 XCDs with private L2s; /opt/skills guide, "in-launch combine"): plain slab stores -> every wave
 // s_waitcnt vmcnt(0) -> barrier -> lane 0: agent-scope RELEASE fence, s_waitcnt vmcnt(0), relaxed agent-scope ticket fetch_add; the last
 // arriver: agent-scope ACQUIRE fence (drops its CU's L1) -> barrier -> plain slab loads.  The ticket returns to 0 before the launch ends.
-// The scratch is shared by every launch: launches of ONE stream serialise, so one training stream per process may use these kernels at
-// a time (jatts_amd.training does).
+// Launches that share a scratch must be stream-ordered (include/jatts_hip.h: jatts_scratch); the library keeps no scratch of its own.
 #pragma once
 #include "common.h"
 
 constexpr int JATTS_WS_TICKETS = 16384;         // uint32 tickets at the head of the scratch (zero between launches)
-struct jatts_ws_t {
-  unsigned* tickets;
+struct jatts_ws_t {                             // the two kernel arguments, in the kernels' order
   float* slabs;
-  int64_t slab_floats;
+  unsigned* tickets;
 };
-extern jatts_ws_t jatts_g_ws;                                  // api.hip: jatts_set_workspace
-int jatts_ws_need(int64_t groups, int64_t slab_floats);        // JATTS_OK, or an error naming the bytes jatts_set_workspace must provide
+// api.hip: *ws = the halves of `scratch` when it is a valid jatts_scratch with `groups` tickets and `slab_floats` f32 of slabs -> JATTS_OK;
+// else JATTS_ERR_ARG (too small: the message names the bytes of slabs the launch needs) and *ws untouched.  Call it among the argument
+// checks, before the first launch.
+int jatts_ws_need(const jatts_scratch* scratch, int64_t groups, int64_t slab_floats, jatts_ws_t* ws);
 
 namespace {
 

@@ -147,7 +147,8 @@ __global__ __launch_bounds__(256) void token_average_kernel(jatts_ragged rg_tok,
 #define S_ ((hipStream_t)stream)
 
 extern "C" int jatts_stft_mag(const jatts_ragged* rg_frames, const int32_t* cu_samples, const int32_t* host_samples, const float* x,
-                              const float* table, int32_t n_fft, int32_t hop, float* mag, int32_t ldo, float* pow_sum, void* stream) {
+                              const float* table, int32_t n_fft, int32_t hop, float* mag, int32_t ldo, float* pow_sum, const jatts_scratch* scratch,
+                              void* stream) {
   if (!rg_frames || !cu_samples || !host_samples || !x || !table || !mag) return jatts_set_error_msg(JATTS_ERR_ARG, "stft_mag: null pointer");
   if (n_fft < 64 || n_fft > 2048 || n_fft % 64) return jatts_set_error_msg(JATTS_ERR_ARG, "stft_mag: n_fft must be a multiple of 64, at most 2048");
   if (hop < 1 || hop > n_fft) return jatts_set_error_msg(JATTS_ERR_ARG, "stft_mag: hop must lie in [1, n_fft]");
@@ -167,12 +168,10 @@ extern "C" int jatts_stft_mag(const jatts_ragged* rg_frames, const int32_t* cu_s
   if (max_frames != rg_frames->max_len) return jatts_set_error_msg(JATTS_ERR_ARG, "stft_mag: frame geometry is not 1 + n_samples / hop");
   if (rows >= (int64_t)1 << 31) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "stft_mag: launch too large");
   const int n_tiles = (nbp + BW - 1) / BW;
-  float* part = nullptr;
-  if (pow_sum) {
-    const int rc = jatts_ws_need(0, (int64_t)n_tiles * rows);
-    if (rc != JATTS_OK) return rc;
-    part = jatts_g_ws.slabs;
-  }
+  jatts_ws_t ws = {nullptr, nullptr};       // slabs only: one float per (bin tile, frame), summed per frame by pow_finish_kernel
+  if (pow_sum)
+    if (const int rc = jatts_ws_need(scratch, 0, (int64_t)n_tiles * rows, &ws)) return rc;
+  float* part = ws.slabs;
   jatts_ragged rg = *rg_frames;
   rg.total_rows = (int32_t)rows;
   rg.host_lens = nullptr;

@@ -1024,24 +1024,19 @@ inline unsigned blocks_for(int64_t n, int per_block, unsigned cap = 8192) {
 #define S_ ((hipStream_t)stream)
 #define NULLCHK(cond, msg) \
   if (cond) return jatts_set_error_msg(JATTS_ERR_ARG, msg)
-// scratch of the deterministic reductions (det_reduce.h): `groups` tickets, `floats` f32 of slabs
-#define WS_NEED(groups, floats)                                        \
-  do {                                                                 \
-    const int rc_ = jatts_ws_need((int64_t)(groups), (int64_t)(floats)); \
-    if (rc_ != JATTS_OK) return rc_;                                   \
-  } while (0)
-#define WS_ jatts_g_ws.slabs, jatts_g_ws.tickets
 
 extern "C" int jatts_layernorm_bwd(const float* x, int32_t ldx, const float* dy, int32_t lddy, const float* gamma, int64_t rows, int32_t dim,
-                                   float eps, float* dx, int32_t lddx, float* dgamma, float* dbeta, void* stream) {
+                                   float eps, float* dx, int32_t lddx, float* dgamma, float* dbeta, const jatts_scratch* scratch, void* stream) {
   NULLCHK(!x || !dy || !gamma, "layernorm_bwd: null pointer");
   NULLCHK((dgamma == nullptr) != (dbeta == nullptr), "layernorm_bwd: dgamma and dbeta go together");
   if (dim < 1 || dim > 64 * LN_MAXPL) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "layernorm_bwd: 1 <= dim <= 1536");
   if (rows <= 0) return JATTS_OK;
   // <= 512 workgroups (8 waves per CU over the chip): the last arriver adds up one [dgamma | dbeta] slab per workgroup
   const unsigned nb = blocks_for(rows, 16, 512);
-  if (dgamma) WS_NEED((nb + LN_GROUP - 1) / LN_GROUP + 1, (int64_t)(nb + (nb + LN_GROUP - 1) / LN_GROUP) * 2 * dim);
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nb), dim3(256), 0, S_, x, ldx, dy, lddy, gamma, rows, dim, eps, dx, lddx, dgamma, dbeta, WS_);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (dgamma) 
+    if (const int rc = jatts_ws_need(scratch, (nb + LN_GROUP - 1) / LN_GROUP + 1, (int64_t)(nb + (nb + LN_GROUP - 1) / LN_GROUP) * 2 * dim, &ws)) return rc;
+  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nb), dim3(256), 0, S_, x, ldx, dy, lddy, gamma, rows, dim, eps, dx, lddx, dgamma, dbeta, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
@@ -1092,7 +1087,7 @@ extern "C" int jatts_dwconv(const jatts_ragged* rg, const float* x, const float*
   return JATTS_OK;
 }
 extern "C" int jatts_dwconv_wgrad(const jatts_ragged* rg, const float* x, const float* dy, float* dw, int32_t dim, int32_t k_w, int32_t pad,
-                                  void* stream) {
+                                  const jatts_scratch* scratch, void* stream) {
   NULLCHK(!rg || !x || !dy || !dw, "dwconv_wgrad: null pointer");
   NULLCHK(dim < 1 || k_w < 1 || k_w > DW_KMAX, "dwconv_wgrad: 1 <= k_w <= 32");
   if (rg->n_seq <= 0 || rg->max_len <= 0) return JATTS_OK;
@@ -1100,29 +1095,32 @@ extern "C" int jatts_dwconv_wgrad(const jatts_ragged* rg, const float* x, const 
     const int tiles = (rg->max_len + DWT - 1) / DWT;
     const int tpb = tiles > 8 ? 4 : 1;     // a few tiles per workgroup: 4x fewer slabs to sum on long sequences
     const dim3 tgrid((unsigned)((tiles + tpb - 1) / tpb), (unsigned)rg->n_seq, (unsigned)((dim + 63) / 64));
-    WS_NEED(tgrid.z, (int64_t)tgrid.x * tgrid.y * tgrid.z * 64 * k_w);
-    if (k_w == 7) hipLaunchKernelGGL(dwconv_wgrad_tiled_kernel<7>, tgrid, dim3(256), 0, S_, *rg, x, dy, dw, dim, pad, tpb, WS_);
-    else hipLaunchKernelGGL(dwconv_wgrad_tiled_kernel<31>, tgrid, dim3(256), 0, S_, *rg, x, dy, dw, dim, pad, tpb, WS_);
+    jatts_ws_t ws = {nullptr, nullptr};
+    if (const int rc = jatts_ws_need(scratch, tgrid.z, (int64_t)tgrid.x * tgrid.y * tgrid.z * 64 * k_w, &ws)) return rc;
+    if (k_w == 7) hipLaunchKernelGGL(dwconv_wgrad_tiled_kernel<7>, tgrid, dim3(256), 0, S_, *rg, x, dy, dw, dim, pad, tpb, ws.slabs, ws.tickets);
+    else hipLaunchKernelGGL(dwconv_wgrad_tiled_kernel<31>, tgrid, dim3(256), 0, S_, *rg, x, dy, dw, dim, pad, tpb, ws.slabs, ws.tickets);
     JATTS_CHECK_LAUNCH();
     return JATTS_OK;
   }
   unsigned gz = (unsigned)((rg->max_len + 63) / 64);
   if (gz > 64) gz = 64;
-  WS_NEED((dim + 63) / 64, (int64_t)((dim + 63) / 64) * rg->n_seq * gz * 64 * k_w);
-  hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3((unsigned)((dim + 63) / 64), (unsigned)rg->n_seq, gz), dim3(256), 0, S_, *rg, x, dy, dw, dim, k_w, pad, WS_);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (const int rc = jatts_ws_need(scratch, (dim + 63) / 64, (int64_t)((dim + 63) / 64) * rg->n_seq * gz * 64 * k_w, &ws)) return rc;
+  hipLaunchKernelGGL(dwconv_wgrad_kernel, dim3((unsigned)((dim + 63) / 64), (unsigned)rg->n_seq, gz), dim3(256), 0, S_, *rg, x, dy, dw, dim, k_w, pad, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
 
 extern "C" int jatts_col_stats(const float* x, const float* y2, int32_t ld, int64_t rows, int32_t dim, const float* shift, const float* mul,
-                               int32_t mode, float* out0, float* out1, void* stream) {
+                               int32_t mode, float* out0, float* out1, const jatts_scratch* scratch, void* stream) {
   NULLCHK(!x || !out0 || !out1 || (mode == 1 && !y2), "col_stats: null pointer");
   NULLCHK(mode != 0 && mode != 1, "col_stats: mode 0 (moments) or 1 (dy sums)");
   if (rows <= 0 || dim <= 0) return JATTS_OK;
   const int64_t gy0 = (rows + 255) / 256;
   const unsigned gx = (unsigned)((dim + 63) / 64), gy = (unsigned)(gy0 < 256 ? gy0 : 256);
-  WS_NEED(gx, (int64_t)gx * gy * 128);
-  hipLaunchKernelGGL(col_stats_kernel, dim3(gx, gy), dim3(256), 0, S_, x, y2, ld, rows, dim, shift, mul, mode, out0, out1, WS_);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (const int rc = jatts_ws_need(scratch, gx, (int64_t)gx * gy * 128, &ws)) return rc;
+  hipLaunchKernelGGL(col_stats_kernel, dim3(gx, gy), dim3(256), 0, S_, x, y2, ld, rows, dim, shift, mul, mode, out0, out1, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
@@ -1225,13 +1223,15 @@ extern "C" int jatts_outer_rows(const float* v, const float* w, const float* bia
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
-extern "C" int jatts_col_wsum(const float* x, int32_t ld, const float* v, int64_t rows, int32_t dim, float* out, void* stream) {
+extern "C" int jatts_col_wsum(const float* x, int32_t ld, const float* v, int64_t rows, int32_t dim, float* out, const jatts_scratch* scratch,
+                              void* stream) {
   NULLCHK(!x || !v || !out, "col_wsum: null pointer");
   if (rows <= 0 || dim <= 0) return JATTS_OK;
   const int64_t gy0 = (rows + 255) / 256;
   const unsigned gx = (unsigned)((dim + 63) / 64), gy = (unsigned)(gy0 < 256 ? gy0 : 256);
-  WS_NEED(gx, (int64_t)gx * gy * 64);
-  hipLaunchKernelGGL(col_wsum_kernel, dim3(gx, gy), dim3(256), 0, S_, x, ld, v, rows, dim, out, WS_);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (const int rc = jatts_ws_need(scratch, gx, (int64_t)gx * gy * 64, &ws)) return rc;
+  hipLaunchKernelGGL(col_wsum_kernel, dim3(gx, gy), dim3(256), 0, S_, x, ld, v, rows, dim, out, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
@@ -1274,7 +1274,7 @@ extern "C" int jatts_qkv_split(const float* qkv, const float* u, const float* v,
   return JATTS_OK;
 }
 extern "C" int jatts_qkv_split_bwd(const float* dqu, const float* dqv, const float* dk, const float* dvv, int32_t n_batch, int32_t t_len,
-                                   int32_t n_heads, int32_t d_k, float* dqkv, float* du, float* dv, void* stream) {
+                                   int32_t n_heads, int32_t d_k, float* dqkv, float* du, float* dv, const jatts_scratch* scratch, void* stream) {
   NULLCHK(!dqu || !dk || !dvv || !dqkv || (!dqv != !dv) || (!du != !dv), "qkv_split_bwd: null pointer");
   NULLCHK(n_batch < 1 || t_len < 1 || n_heads < 1 || d_k < 1, "qkv_split_bwd: bad geometry");
   const int64_t rows = (int64_t)n_batch * t_len;
@@ -1282,8 +1282,10 @@ extern "C" int jatts_qkv_split_bwd(const float* dqu, const float* dqv, const flo
   int rpb = 32;
   while ((rows + rpb - 1) / rpb > 512) rpb += 32;
   const unsigned nb = (unsigned)((rows + rpb - 1) / rpb);
-  if (du || dv) WS_NEED((nb + LN_GROUP - 1) / LN_GROUP + 1, (int64_t)(nb + (nb + LN_GROUP - 1) / LN_GROUP) * 2 * n_heads * d_k);
-  hipLaunchKernelGGL(qkv_split_bwd_kernel, dim3(nb), dim3(256), 0, S_, dqu, dqv, dk, dvv, n_batch, t_len, n_heads, d_k, dqkv, du, dv, rpb, WS_);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (du || dv) 
+    if (const int rc = jatts_ws_need(scratch, (nb + LN_GROUP - 1) / LN_GROUP + 1, (int64_t)(nb + (nb + LN_GROUP - 1) / LN_GROUP) * 2 * n_heads * d_k, &ws)) return rc;
+  hipLaunchKernelGGL(qkv_split_bwd_kernel, dim3(nb), dim3(256), 0, S_, dqu, dqv, dk, dvv, n_batch, t_len, n_heads, d_k, dqkv, du, dv, rpb, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
@@ -1307,12 +1309,13 @@ extern "C" int jatts_dropout_add(const float* x, const float* resid, float* y, i
   return JATTS_OK;
 }
 
-extern "C" int jatts_sumsq(const float* x, int64_t n, double* out, void* stream) {
+extern "C" int jatts_sumsq(const float* x, int64_t n, double* out, const jatts_scratch* scratch, void* stream) {
   NULLCHK(!x || !out, "sumsq: null pointer");
   if (n <= 0) return JATTS_OK;
   const unsigned nb = blocks_for(n, 4096, 1024);
-  WS_NEED(1, (int64_t)nb * 2);
-  hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, S_, x, n, out, (double*)jatts_g_ws.slabs, jatts_g_ws.tickets);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (const int rc = jatts_ws_need(scratch, 1, (int64_t)nb * 2, &ws)) return rc;
+  hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, S_, x, n, out, (double*)ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
@@ -1363,15 +1366,18 @@ extern "C" int jatts_groupnorm_fwd(const jatts_ragged* rg, const float* x, int32
   return JATTS_OK;
 }
 extern "C" int jatts_groupnorm_bwd(const jatts_ragged* rg, const float* x, const float* dy, int32_t dim, int32_t groups, const float* gamma,
-                                   const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta, void* stream) {
+                                   const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta, const jatts_scratch* scratch,
+                                   void* stream) {
   NULLCHK(!rg || !x || !dy || !gamma || !mean || !rstd, "groupnorm_bwd: null pointer");
   NULLCHK((dgamma == nullptr) != (dbeta == nullptr), "groupnorm_bwd: dgamma and dbeta go together");
   NULLCHK(groups < 1 || dim % groups != 0 || dim / groups > 256 || 256 % (dim / groups) != 0,
           "groupnorm_bwd: channels per group must divide 256");
   if (rg->n_seq <= 0 || rg->max_len <= 0) return JATTS_OK;
-  if (dgamma) WS_NEED(groups, (int64_t)rg->n_seq * 2 * dim);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (dgamma) 
+    if (const int rc = jatts_ws_need(scratch, groups, (int64_t)rg->n_seq * 2 * dim, &ws)) return rc;
   hipLaunchKernelGGL(groupnorm_bwd_kernel, dim3((unsigned)groups, (unsigned)rg->n_seq), dim3(256), 0, S_, *rg, x, dy, dim, groups, gamma, mean, rstd, dx,
-                     dgamma, dbeta, WS_);
+                     dgamma, dbeta, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
@@ -1383,13 +1389,14 @@ extern "C" int jatts_snakebeta_fwd(const float* x, float* y, int64_t rows, int32
   return JATTS_OK;
 }
 extern "C" int jatts_snakebeta_bwd(const float* x, const float* dy, int64_t rows, int32_t dim, const float* alpha, const float* beta, float* dx,
-                                   float* dalpha, float* dbeta, void* stream) {
+                                   float* dalpha, float* dbeta, const jatts_scratch* scratch, void* stream) {
   NULLCHK(!x || !dy || !alpha || !beta || !dx || !dalpha || !dbeta, "snakebeta_bwd: null pointer");
   if (rows <= 0 || dim <= 0) return JATTS_OK;
   const int64_t gy0 = (rows + 255) / 256;
   const unsigned gx = (unsigned)((dim + 63) / 64), gy = (unsigned)(gy0 < 256 ? gy0 : 256);
-  WS_NEED(gx, (int64_t)gx * gy * 128);
-  hipLaunchKernelGGL(snakebeta_bwd_kernel, dim3(gx, gy), dim3(256), 0, S_, x, dy, rows, dim, alpha, beta, dx, dalpha, dbeta, WS_);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (const int rc = jatts_ws_need(scratch, gx, (int64_t)gx * gy * 128, &ws)) return rc;
+  hipLaunchKernelGGL(snakebeta_bwd_kernel, dim3(gx, gy), dim3(256), 0, S_, x, dy, rows, dim, alpha, beta, dx, dalpha, dbeta, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
@@ -1407,13 +1414,14 @@ extern "C" int jatts_ctc_forward_sum(const float* log_p, int32_t n_batch, int32_
   return JATTS_OK;
 }
 
-extern "C" int jatts_seq_sum(const jatts_ragged* rg, const float* x, int32_t dim, float* out, void* stream) {
+extern "C" int jatts_seq_sum(const jatts_ragged* rg, const float* x, int32_t dim, float* out, const jatts_scratch* scratch, void* stream) {
   NULLCHK(!rg || !x || !out, "seq_sum: null pointer");
   if (rg->n_seq <= 0 || rg->max_len <= 0 || dim <= 0) return JATTS_OK;
   unsigned gz = (unsigned)((rg->max_len + 63) / 64);
   if (gz > 16) gz = 16;
-  WS_NEED((int64_t)((dim + 63) / 64) * rg->n_seq, (int64_t)((dim + 63) / 64) * rg->n_seq * gz * 64);
-  hipLaunchKernelGGL(seq_sum_kernel, dim3((unsigned)((dim + 63) / 64), (unsigned)rg->n_seq, gz), dim3(256), 0, S_, *rg, x, dim, out, WS_);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (const int rc = jatts_ws_need(scratch, (int64_t)((dim + 63) / 64) * rg->n_seq, (int64_t)((dim + 63) / 64) * rg->n_seq * gz * 64, &ws)) return rc;
+  hipLaunchKernelGGL(seq_sum_kernel, dim3((unsigned)((dim + 63) / 64), (unsigned)rg->n_seq, gz), dim3(256), 0, S_, *rg, x, dim, out, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }

@@ -2,6 +2,8 @@
 // gradients of jatts_conv1d.  The data gradient of a conv is jatts_conv1d itself on flipped, transposed weights.
 // Reference: jatts/trainers/fastspeech2.py:24-100 (_train_step), jatts/losses/{l1l2_loss,duration_predictor_loss,
 // variance_predictor_loss}.py, torch.nn.Conv1d's autograd.
+#include <algorithm>
+
 #include "common.h"
 #include "det_reduce.h"
 #include "resunit_emul16_impl.h"   // acc2x4 / mma16p: the seven-product rule of the emulated convs, shared with the emulated weight gradient below
@@ -611,14 +613,6 @@ __global__ __launch_bounds__(256) void col_sum_ragged_kernel(jatts_ragged rg, co
 
 #define S_ ((hipStream_t)stream)
 
-static int bias_grad_plain(const jatts_ragged* rg, const float* dy, int ldy, int n_out, float* db, void* stream) {
-  const unsigned gx = (unsigned)((n_out + 63) / 64);
-  const int rc = jatts_ws_need(gx, (int64_t)gx * 128 * 64);
-  if (rc != JATTS_OK) return rc;
-  hipLaunchKernelGGL(col_sum_ragged_kernel, dim3(gx, 128), dim3(256), 0, S_, *rg, dy, ldy, n_out, db, 1, jatts_g_ws.slabs, jatts_g_ws.tickets);
-  return JATTS_OK;
-}
-
 extern "C" int jatts_masked_loss(const jatts_ragged* rg, const float* a, int32_t lda, const float* b, int32_t ldb, int32_t dim,
                                  const int32_t* valid_len, int32_t kind, float log_offset, double scale, float* out, double* workspace,
                                  void* stream) {
@@ -653,7 +647,8 @@ static int wgrad_seq_groups(int tiles_m, int n_seq) {
 }
 
 extern "C" int jatts_conv1d_wgrad(const jatts_ragged* rg, const float* x, int32_t ldx, const float* dy, int32_t ldy, int32_t c_in,
-                                  int32_t n_out, int32_t k_w, int32_t dil, int32_t pad, float* dw, float* db, float* workspace, void* stream) {
+                                  int32_t n_out, int32_t k_w, int32_t dil, int32_t pad, float* dw, float* db, float* workspace,
+                                  const jatts_scratch* scratch, void* stream) {
   if (!rg || !x || !dy || !dw) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad: null pointer");
   if (c_in < 1 || n_out < 1 || k_w < 1 || dil < 1) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad: bad geometry");
   if (pad < 0 || (int64_t)pad > (int64_t)(k_w - 1) * dil) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad: pad must lie in [0, (k_w - 1) * dil]");
@@ -681,31 +676,30 @@ extern "C" int jatts_conv1d_wgrad(const jatts_ragged* rg, const float* x, int32_
     JATTS_CHECK_LAUNCH();
     return JATTS_OK;
   }
-  if (db) {
-    const int rc = bias_grad_plain(rg, dy, ldy, n_out, db, stream);
-    if (rc != JATTS_OK) return rc;
-  }
-  // VALU fallback (other kernel widths): deterministic split-K through the library scratch (det_reduce.h); with a workspace argument dw is
-  // OVERWRITTEN (the contract of the MFMA path), without one the result is accumulated into dw
-  {
-    const int rc = jatts_ws_need((int64_t)tiles, (int64_t)tiles * groups * 4096);
-    if (rc != JATTS_OK) return rc;
-  }
-  hipLaunchKernelGGL(conv_wgrad_kernel, dim3((unsigned)((n_out + 63) / 64), (unsigned)((c_in + 63) / 64), (unsigned)(k_w * groups)), dim3(256), 0, S_,
-                     *rg, x, ldx, dy, ldy, c_in, n_out, k_w, dil, pad, groups, dw, workspace ? 1 : 0, jatts_g_ws.slabs, jatts_g_ws.tickets);
+  // VALU fallback (other kernel widths): deterministic split-K through the caller's scratch (det_reduce.h); with a workspace argument dw is
+  // OVERWRITTEN (the contract of the MFMA path), without one the result is accumulated into dw.  The bias sum (one group per 64 channels,
+  // 128 parts) runs first through the same scratch, stream-ordered: one check for the larger of the two, before either launch.
+  const unsigned gx = (unsigned)((n_out + 63) / 64);
+  const int64_t bias_floats = db ? (int64_t)gx * 128 * 64 : 0;
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (const int rc = jatts_ws_need(scratch, std::max<int64_t>(tiles, gx), std::max((int64_t)tiles * groups * 4096, bias_floats), &ws)) return rc;
+  if (db) hipLaunchKernelGGL(col_sum_ragged_kernel, dim3(gx, 128), dim3(256), 0, S_, *rg, dy, ldy, n_out, db, 1, ws.slabs, ws.tickets);
+  hipLaunchKernelGGL(conv_wgrad_kernel, dim3(gx, (unsigned)((c_in + 63) / 64), (unsigned)(k_w * groups)), dim3(256), 0, S_,
+                     *rg, x, ldx, dy, ldy, c_in, n_out, k_w, dil, pad, groups, dw, workspace ? 1 : 0, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }
 
 extern "C" int jatts_conv1d_wgrad_emul(const jatts_ragged* rg, const float* x, int32_t ldx, const float* dy, int32_t ldy, int32_t c_in, int32_t n_out,
-                                       int32_t k_w, int32_t dil, int32_t pad, int32_t dtype, float* dw, float* db, float* workspace, void* stream) {
+                                       int32_t k_w, int32_t dil, int32_t pad, int32_t dtype, float* dw, float* db, float* workspace,
+                                       const jatts_scratch* scratch, void* stream) {
   if (dtype == JATTS_F32E6) return jatts_set_error_msg(JATTS_ERR_UNSUPPORTED, "conv1d_wgrad_emul: the six-product arithmetic (JATTS_F32E6) has no weight gradient");
   if (dtype != JATTS_F32E) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: dtype must be JATTS_F32E");
   if (!rg || !x || !dy || !dw) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: null pointer");
   if (c_in < 1 || n_out < 1 || k_w < 1 || dil < 1) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: bad geometry");
   if (pad < 0 || (int64_t)pad > (int64_t)(k_w - 1) * dil) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: pad must lie in [0, (k_w - 1) * dil]");
   // outside the emulated kernel's taps / halo: the exact-f32 entry (the more accurate of the two)
-  if (!(k_w == 1 || k_w == 3 || k_w == 5) || (k_w - 1) * dil > WE_HALO) return jatts_conv1d_wgrad(rg, x, ldx, dy, ldy, c_in, n_out, k_w, dil, pad, dw, db, workspace, stream);
+  if (!(k_w == 1 || k_w == 3 || k_w == 5) || (k_w - 1) * dil > WE_HALO) return jatts_conv1d_wgrad(rg, x, ldx, dy, ldy, c_in, n_out, k_w, dil, pad, dw, db, workspace, scratch, stream);
   if (rg->n_seq <= 0 || rg->max_len <= 0) return JATTS_OK;
   if (!workspace) return jatts_set_error_msg(JATTS_ERR_ARG, "conv1d_wgrad_emul: needs the split-K workspace of jatts_conv1d_wgrad (see include/jatts_hip.h)");
   const int tiles_m = ((n_out + 63) / 64) * ((c_in + 63) / 64);
@@ -729,16 +723,14 @@ extern "C" int jatts_conv1d_wgrad_emul(const jatts_ragged* rg, const float* x, i
   return JATTS_OK;
 }
 
-extern "C" int jatts_col_sum(const float* x, int32_t ld, int64_t rows, int32_t dim, float* out, void* stream) {
+extern "C" int jatts_col_sum(const float* x, int32_t ld, int64_t rows, int32_t dim, float* out, const jatts_scratch* scratch, void* stream) {
   if (!x || !out) return jatts_set_error_msg(JATTS_ERR_ARG, "col_sum: null pointer");
   if (rows <= 0 || dim <= 0) return JATTS_OK;
   const int64_t gy0 = (rows + 255) / 256;
   const unsigned gx = (unsigned)((dim + 63) / 64), gy = (unsigned)(gy0 < 256 ? gy0 : 256);
-  {
-    const int rc = jatts_ws_need(gx, (int64_t)gx * gy * 64);
-    if (rc != JATTS_OK) return rc;
-  }
-  hipLaunchKernelGGL(col_sum_kernel, dim3(gx, gy), dim3(256), 0, S_, x, ld, rows, dim, out, 0, jatts_g_ws.slabs, jatts_g_ws.tickets);
+  jatts_ws_t ws = {nullptr, nullptr};
+  if (const int rc = jatts_ws_need(scratch, gx, (int64_t)gx * gy * 64, &ws)) return rc;
+  hipLaunchKernelGGL(col_sum_kernel, dim3(gx, gy), dim3(256), 0, S_, x, ld, rows, dim, out, 0, ws.slabs, ws.tickets);
   JATTS_CHECK_LAUNCH();
   return JATTS_OK;
 }

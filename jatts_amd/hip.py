@@ -160,57 +160,42 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-_WS = {}               # device -> the zero-initialised scratch of the deterministic reductions (include/jatts_hip.h: jatts_set_workspace)
-_WS_CURRENT = [None]
-_WS_OWNER = {}         # device -> (stream handle, event recorded behind that stream's last reduction launch)
+_WS = {}               # str(device) -> the zero-initialised scratch of the deterministic reductions (include/jatts_hip.h: jatts_scratch)
+_WS_OWNER = {}         # str(device) -> (stream handle, event recorded behind that stream's last reduction launch)
 WS_BYTES = 64 * 1024 + 96 * 1024 * 1024
 
 
-def _ws(device):
+@contextlib.contextmanager
+def _scratch(device):
     """(Graph replays: a captured step bakes the scratch in and is ordered against other users only on the stream it was CAPTURED on -- replay a trainer's
     graph on its capture stream, which is what jatts_amd.training does; ownership is not tracked for replays on other streams.)
-    Register this device's scratch with the library before a kernel that reduces across workgroups (LayerNorm / GroupNorm / SnakeBeta
-    parameter gradients, column sums, depthwise-conv weights, the gradient norm): allocated once, outside any graph capture (the trainers'
-    first step of a signature runs eagerly), kept alive for the life of the process -- a captured step bakes its address in."""
+    Around a kernel that reduces across workgroups (LayerNorm / GroupNorm / SnakeBeta parameter gradients, column sums, depthwise-conv
+    weights, the gradient norm): yields this device's jatts_scratch, by reference, for the call's `scratch` argument.  The buffer is
+    allocated once, outside any graph capture (the trainers' first step of a signature runs eagerly), and kept alive for the life of the
+    process -- a captured step bakes its address in."""
     key = str(device)
-    # ONE scratch (tickets + slabs) per device: two streams reducing concurrently would corrupt each other's tickets silently (ADVICE r4).
-    # The stream that used it last owns it; another stream first waits for that stream's last reduction (an event, no host sync).  During a
-    # graph capture the scratch belongs to the capturing stream for the graph's whole life (the trainers capture on one stream).
-    if not torch.cuda.is_current_stream_capturing():
-        cur = torch.cuda.current_stream(device)
-        own = _WS_OWNER.get(key)
-        if own is not None and own[0] != cur.cuda_stream and not own[1].query():
-            cur.wait_event(own[1])
-        ev = own[1] if (own is not None and own[0] == cur.cuda_stream) else torch.cuda.Event()
-        _WS_OWNER[key] = (cur.cuda_stream, ev)
-        _WS_PENDING[0] = (cur, ev)
-    if _WS_CURRENT[0] == key:
-        return
+    capturing = torch.cuda.is_current_stream_capturing()
     buf = _WS.get(key)
     if buf is None:
-        if torch.cuda.is_current_stream_capturing():
+        if capturing:
             raise _abi.JattsHipError("the reduction scratch must exist before a graph capture: run one eager step first")
         buf = _WS[key] = torch.zeros(WS_BYTES, dtype=torch.uint8, device=device)
         torch.cuda.current_stream(device).synchronize()
-    _abi.check(_abi.load().jatts_set_workspace(buf.data_ptr(), buf.numel()), "jatts_set_workspace")
-    _WS_CURRENT[0] = key
-
-
-_WS_PENDING = [None]
-
-
-def _ws_done():
-    """Behind a reduction launch: mark how far the owning stream has got with the scratch (what another stream would wait for)."""
-    p, _WS_PENDING[0] = _WS_PENDING[0], None
-    if p is not None:
-        p[1].record(p[0])
-
-
-def _ws_check(rc, name):
+    # ONE scratch (tickets + slabs) per device: two streams reducing concurrently would corrupt each other's tickets silently (ADVICE r4).
+    # The stream that used it last owns it; another stream first waits for that stream's last reduction (an event, no host sync).  During a
+    # graph capture the scratch belongs to the capturing stream for the graph's whole life (the trainers capture on one stream).
+    cur = None if capturing else torch.cuda.current_stream(device)
+    if cur is not None:
+        own = _WS_OWNER.get(key)
+        if own is None or own[0] != cur.cuda_stream:
+            if own is not None and not own[1].query():
+                cur.wait_event(own[1])
+            own = _WS_OWNER[key] = (cur.cuda_stream, torch.cuda.Event())
     try:
-        _abi.check(rc, name)
-    finally:          # a failed launch must not leave the pending marker behind: the next reduction would record its event on the wrong stream (ADVICE r5)
-        _ws_done()
+        yield C.byref(_abi.Scratch(buf.data_ptr(), buf.numel()))
+    finally:          # launched or refused: how far the owning stream has got with the scratch (what another stream would wait for)
+        if cur is not None:
+            own[1].record(cur)
 
 
 def _ptr(t, col0=0):
@@ -1403,14 +1388,9 @@ def stft_mag(rb_frames, cu_samples, n_samples, x, table, n_fft, hop, ldo, want_p
     pw = torch.empty(rb_frames.total, dtype=torch.float32, device=x.device) if want_pow else None
     ns = (C.c_int32 * len(n_samples))(*[int(v) for v in n_samples])
     rg = rb_frames.struct()
-    if want_pow:
-        _ws(x.device)
-    rc = lib.jatts_stft_mag(C.byref(rg), _dev(cu_samples).data_ptr(), ns, x.data_ptr(), table.data_ptr(), n_fft, hop,
-                            out.data_ptr(), ldo, _ptr(pw), _stream())
-    if want_pow:
-        _ws_check(rc, "jatts_stft_mag")
-    else:
-        _abi.check(rc, "jatts_stft_mag")
+    with _scratch(x.device) if want_pow else contextlib.nullcontext() as sc:      # only the energy sum reduces: NULL without it
+        _abi.check(lib.jatts_stft_mag(C.byref(rg), _dev(cu_samples).data_ptr(), ns, x.data_ptr(), table.data_ptr(), n_fft, hop,
+                                      out.data_ptr(), ldo, _ptr(pw), sc, _stream()), "jatts_stft_mag")
     _count(2.0 * n_fft * table.shape[-1] * rb_frames.total)
     return out, pw
 
@@ -1844,13 +1824,13 @@ def conv1d_wgrad(rb, x, dy, c_in, n_out, k_w, dil, pad, len_mul=1, want_db=False
                      device=x.device)                                                                                   # split-K partials
     rg = rb.struct(len_mul)
     _count(2.0 * c_in * n_out * k_w * rb.total * len_mul)
-    _ws(x.device)
-    if dtype == F32E:
-        _ws_check(lib.jatts_conv1d_wgrad_emul(C.byref(rg), _dev(x).data_ptr(), x.shape[1], dy.data_ptr(), dy.shape[1], c_in, n_out, k_w, dil,
-                                               pad, dtype, dw.data_ptr(), _ptr(db), ws.data_ptr(), _stream()), "jatts_conv1d_wgrad_emul")
-    else:
-        _ws_check(lib.jatts_conv1d_wgrad(C.byref(rg), _dev(x).data_ptr(), x.shape[1], dy.data_ptr(), dy.shape[1], c_in, n_out, k_w, dil,
-                                          pad, dw.data_ptr(), _ptr(db), ws.data_ptr(), _stream()), "jatts_conv1d_wgrad")
+    with _scratch(x.device) as sc:
+        if dtype == F32E:
+            _abi.check(lib.jatts_conv1d_wgrad_emul(C.byref(rg), _dev(x).data_ptr(), x.shape[1], dy.data_ptr(), dy.shape[1], c_in, n_out, k_w, dil,
+                                                    pad, dtype, dw.data_ptr(), _ptr(db), ws.data_ptr(), sc, _stream()), "jatts_conv1d_wgrad_emul")
+        else:
+            _abi.check(lib.jatts_conv1d_wgrad(C.byref(rg), _dev(x).data_ptr(), x.shape[1], dy.data_ptr(), dy.shape[1], c_in, n_out, k_w, dil,
+                                               pad, dw.data_ptr(), _ptr(db), ws.data_ptr(), sc, _stream()), "jatts_conv1d_wgrad")
     return (dw, db) if want_db else dw
 
 
@@ -1858,8 +1838,8 @@ def col_sum(x, dim=None):
     lib = _abi.load()
     dim = dim or x.shape[1]
     out = _zeros((dim), x.device)
-    _ws(x.device)
-    _ws_check(lib.jatts_col_sum(_dev(x).data_ptr(), x.shape[1], x.shape[0], dim, out.data_ptr(), _stream()), "jatts_col_sum")
+    with _scratch(x.device) as sc:
+        _abi.check(lib.jatts_col_sum(_dev(x).data_ptr(), x.shape[1], x.shape[0], dim, out.data_ptr(), sc, _stream()), "jatts_col_sum")
     return out
 
 
@@ -1881,9 +1861,9 @@ def layernorm_bwd(x, dy, gamma, eps, need_dx=True, need_dparam=True):
     dx = torch.empty_like(x) if need_dx else None
     dg = _zeros((dim), x.device) if need_dparam else None
     db = _zeros((dim), x.device) if need_dparam else None
-    _ws(x.device)
-    _ws_check(lib.jatts_layernorm_bwd(x.data_ptr(), dim, dy.data_ptr(), dim, _f32c(gamma).data_ptr(), rows, dim, float(eps), _ptr(dx), dim,
-                                       _ptr(dg), _ptr(db), _stream()), "jatts_layernorm_bwd")
+    with _scratch(x.device) as sc:
+        _abi.check(lib.jatts_layernorm_bwd(x.data_ptr(), dim, dy.data_ptr(), dim, _f32c(gamma).data_ptr(), rows, dim, float(eps), _ptr(dx), dim,
+                                            _ptr(dg), _ptr(db), sc, _stream()), "jatts_layernorm_bwd")
     return dx, dg, db
 
 
@@ -1936,9 +1916,9 @@ def dwconv_wgrad(rb, x, dy, k_w, pad):
     x, dy = _f32c(x), _f32c(dy)
     dw = _zeros((x.shape[1], k_w), x.device)
     rg = rb.struct()
-    _ws(x.device)
-    _ws_check(lib.jatts_dwconv_wgrad(C.byref(rg), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), x.shape[1], k_w, pad, _stream()),
-               "jatts_dwconv_wgrad")
+    with _scratch(x.device) as sc:
+        _abi.check(lib.jatts_dwconv_wgrad(C.byref(rg), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), x.shape[1], k_w, pad, sc, _stream()),
+                    "jatts_dwconv_wgrad")
     return dw
 
 
@@ -1949,9 +1929,9 @@ def col_stats(x, y2=None, shift=None, mul=None):
     rows, dim = x.shape
     o0 = _zeros((dim), x.device)
     o1 = _zeros((dim), x.device)
-    _ws(x.device)
-    _ws_check(lib.jatts_col_stats(x.data_ptr(), _ptr(y2), dim, rows, dim, _ptr(shift), _ptr(mul), 0 if y2 is None else 1, o0.data_ptr(),
-                                   o1.data_ptr(), _stream()), "jatts_col_stats")
+    with _scratch(x.device) as sc:
+        _abi.check(lib.jatts_col_stats(x.data_ptr(), _ptr(y2), dim, rows, dim, _ptr(shift), _ptr(mul), 0 if y2 is None else 1, o0.data_ptr(),
+                                        o1.data_ptr(), sc, _stream()), "jatts_col_stats")
     return o0, o1
 
 
@@ -2073,8 +2053,8 @@ def col_wsum(x, v):
     lib = _abi.load()
     x, v = _f32c(x), _f32c(v)
     out = _zeros((x.shape[1]), x.device)
-    _ws(x.device)
-    _ws_check(lib.jatts_col_wsum(x.data_ptr(), x.shape[1], v.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), _stream()), "jatts_col_wsum")
+    with _scratch(x.device) as sc:
+        _abi.check(lib.jatts_col_wsum(x.data_ptr(), x.shape[1], v.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), sc, _stream()), "jatts_col_wsum")
     return out
 
 
@@ -2144,9 +2124,9 @@ def qkv_split_bwd(dqu, dqv, dk_, dvv):
     if dqv is not None:
         dqv = _f32c(dqv)
         du, dv = _zeros((H * dk), dqu.device), _zeros((H * dk), dqu.device)
-    _ws(dqu.device)
-    _ws_check(lib.jatts_qkv_split_bwd(dqu.data_ptr(), _ptr(dqv), dk_.data_ptr(), dvv.data_ptr(), B, T, H, dk, dqkv.data_ptr(), _ptr(du), _ptr(dv),
-                                       _stream()), "jatts_qkv_split_bwd")
+    with _scratch(dqu.device) as sc:
+        _abi.check(lib.jatts_qkv_split_bwd(dqu.data_ptr(), _ptr(dqv), dk_.data_ptr(), dvv.data_ptr(), B, T, H, dk, dqkv.data_ptr(), _ptr(du), _ptr(dv),
+                                            sc, _stream()), "jatts_qkv_split_bwd")
     return dqkv, du, dv
 
 
@@ -2178,8 +2158,8 @@ def sumsq(x, out):
     """out (f64 scalar tensor on the device) += sum x^2"""
     lib = _abi.load()
     x = _f32c(x)
-    _ws(x.device)
-    _ws_check(lib.jatts_sumsq(x.data_ptr(), x.numel(), out.data_ptr(), _stream()), "jatts_sumsq")
+    with _scratch(x.device) as sc:
+        _abi.check(lib.jatts_sumsq(x.data_ptr(), x.numel(), out.data_ptr(), sc, _stream()), "jatts_sumsq")
     return out
 
 
@@ -2232,9 +2212,9 @@ def groupnorm_bwd(rb, x, dy, groups, gamma, mean, rstd, need_dx=True, need_dpara
     dg = _zeros((dim), x.device) if need_dparam else None
     db = _zeros((dim), x.device) if need_dparam else None
     rg = rb.struct()
-    _ws(x.device)
-    _ws_check(lib.jatts_groupnorm_bwd(C.byref(rg), x.data_ptr(), dy.data_ptr(), dim, groups, _f32c(gamma).data_ptr(), mean.data_ptr(),
-                                       rstd.data_ptr(), _ptr(dx), _ptr(dg), _ptr(db), _stream()), "jatts_groupnorm_bwd")
+    with _scratch(x.device) as sc:
+        _abi.check(lib.jatts_groupnorm_bwd(C.byref(rg), x.data_ptr(), dy.data_ptr(), dim, groups, _f32c(gamma).data_ptr(), mean.data_ptr(),
+                                            rstd.data_ptr(), _ptr(dx), _ptr(dg), _ptr(db), sc, _stream()), "jatts_groupnorm_bwd")
     return dx, dg, db
 
 
@@ -2253,9 +2233,9 @@ def snakebeta_bwd(x, dy, alpha, beta):
     dx = torch.empty_like(x)
     da = _zeros((x.shape[1]), x.device)
     db = _zeros((x.shape[1]), x.device)
-    _ws(x.device)
-    _ws_check(lib.jatts_snakebeta_bwd(x.data_ptr(), dy.data_ptr(), x.shape[0], x.shape[1], _f32c(alpha).data_ptr(), _f32c(beta).data_ptr(),
-                                       dx.data_ptr(), da.data_ptr(), db.data_ptr(), _stream()), "jatts_snakebeta_bwd")
+    with _scratch(x.device) as sc:
+        _abi.check(lib.jatts_snakebeta_bwd(x.data_ptr(), dy.data_ptr(), x.shape[0], x.shape[1], _f32c(alpha).data_ptr(), _f32c(beta).data_ptr(),
+                                            dx.data_ptr(), da.data_ptr(), db.data_ptr(), sc, _stream()), "jatts_snakebeta_bwd")
     return dx, da, db
 
 
@@ -2283,8 +2263,8 @@ def seq_sum(rb, x):
     x = _f32c(x)
     out = _zeros((rb.n_seq, x.shape[1]), x.device)
     rg = rb.struct()
-    _ws(x.device)
-    _ws_check(lib.jatts_seq_sum(C.byref(rg), x.data_ptr(), x.shape[1], out.data_ptr(), _stream()), "jatts_seq_sum")
+    with _scratch(x.device) as sc:
+        _abi.check(lib.jatts_seq_sum(C.byref(rg), x.data_ptr(), x.shape[1], out.data_ptr(), sc, _stream()), "jatts_seq_sum")
     return out
 
 

@@ -26,7 +26,7 @@ def test_library_exports_every_declared_symbol(lib):
 def test_ctypes_structs_match_header_field_order():
     hdr = open(os.path.join(ROOT, "include", "jatts_hip.h")).read()
     from jatts_amd import _abi
-    for cname, cls in (("jatts_ragged", _abi.Ragged), ("jatts_conv_desc", _abi.ConvDesc),
+    for cname, cls in (("jatts_ragged", _abi.Ragged), ("jatts_scratch", _abi.Scratch), ("jatts_conv_desc", _abi.ConvDesc),
                        ("jatts_resunit_desc", _abi.ResUnitDesc), ("jatts_relattn_desc", _abi.RelAttnDesc),
                        ("jatts_resblock_desc", _abi.ResBlockDesc)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), hdr, re.S).group(1)

@@ -99,8 +99,8 @@ def test_decode_cli_knows_the_attention_flag():
     assert '${attention_precision:+--attention-precision "${attention_precision}"}' in sh
 
 
-def test_abi_version_7_everywhere(lib):
+def test_abi_version_8_everywhere(lib):
     hdr = open(os.path.join(ROOT, "include", "jatts_hip.h")).read()
     from jatts_amd import _abi
-    assert int(re.search(r"#define JATTS_ABI_VERSION (\d+)", hdr).group(1)) == 7
-    assert lib.jatts_abi_version() == 7 and _abi.ABI_VERSION == 7
+    assert int(re.search(r"#define JATTS_ABI_VERSION (\d+)", hdr).group(1)) == 8
+    assert lib.jatts_abi_version() == 8 and _abi.ABI_VERSION == 8

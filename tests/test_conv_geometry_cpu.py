@@ -169,9 +169,9 @@ def test_entry_points_refuse_a_pad_outside_the_taps(lib):
         d.pad = pad
         assert lib.jatts_conv1d(C.byref(d), None) == -1 and b"pad must lie in" in lib.jatts_last_error()
         rg = _abi.Ragged(p, 1, 0, 1, 0, None)
-        assert lib.jatts_conv1d_wgrad(C.byref(rg), p, 64, p, 32, 64, 32, k, dil, ok_pad, p, None, p, None) == 0
-        assert lib.jatts_conv1d_wgrad(C.byref(rg), p, 64, p, 32, 64, 32, k, dil, pad, p, None, p, None) == -1
+        assert lib.jatts_conv1d_wgrad(C.byref(rg), p, 64, p, 32, 64, 32, k, dil, ok_pad, p, None, p, None, None) == 0
+        assert lib.jatts_conv1d_wgrad(C.byref(rg), p, 64, p, 32, 64, 32, k, dil, pad, p, None, p, None, None) == -1
         assert b"pad must lie in" in lib.jatts_last_error()
-        assert lib.jatts_conv1d_wgrad_emul(C.byref(rg), p, 64, p, 32, 64, 32, k, dil, ok_pad, _abi.F32E, p, None, p, None) == 0
-        assert lib.jatts_conv1d_wgrad_emul(C.byref(rg), p, 64, p, 32, 64, 32, k, dil, pad, _abi.F32E, p, None, p, None) == -1
+        assert lib.jatts_conv1d_wgrad_emul(C.byref(rg), p, 64, p, 32, 64, 32, k, dil, ok_pad, _abi.F32E, p, None, p, None, None) == 0
+        assert lib.jatts_conv1d_wgrad_emul(C.byref(rg), p, 64, p, 32, 64, 32, k, dil, pad, _abi.F32E, p, None, p, None, None) == -1
         assert b"conv1d_wgrad_emul: pad must lie in" in lib.jatts_last_error()

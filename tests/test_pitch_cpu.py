@@ -113,5 +113,5 @@ def test_new_symbols_are_declared_with_their_citation(lib):
         m = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int %s\(" % name, hdr, re.S)
         assert m and re.search(r"dio\.py:\d+", m.group(1)), name
     assert "UNPINNED" in hdr[hdr.index("Stage-1 pitch"):hdr.index("jatts_acf_from_mag(")]
-    assert _abi.ABI_VERSION == 7 and lib.jatts_abi_version() == 7
+    assert _abi.ABI_VERSION == 8 and lib.jatts_abi_version() == 8
     assert "pitch.hip" in open(os.path.join(ROOT, "jatts_amd", "csrc", "Makefile")).read()

@@ -181,7 +181,7 @@ def test_new_symbols_are_declared_with_their_citation():
     from jatts_amd import _abi
     for name in ("jatts_resample", "jatts_wave_gain_peak"):
         assert name in _abi.PROTOTYPES and f"int {name}(" in hdr
-    assert "utils/utils.py:201-234" in hdr and "#define JATTS_ABI_VERSION 7" in hdr
+    assert "utils/utils.py:201-234" in hdr and "#define JATTS_ABI_VERSION 8" in hdr
     assert "resample.hip" in open(os.path.join(ROOT, "jatts_amd", "csrc", "Makefile")).read()
 
 

@@ -91,7 +91,7 @@ def test_new_symbols_in_header_mirror_and_library(lib):
     declared = set(re.findall(r"\b(jatts_[a-z0-9_]+)\s*\(", hdr))
     for name in NEW_SYMBOLS:
         assert name in declared and name in _abi.PROTOTYPES and hasattr(lib, name), name
-    assert int(re.search(r"#define JATTS_ABI_VERSION (\d+)", hdr).group(1)) == 7 == _abi.ABI_VERSION == lib.jatts_abi_version()
+    assert int(re.search(r"#define JATTS_ABI_VERSION (\d+)", hdr).group(1)) == 8 == _abi.ABI_VERSION == lib.jatts_abi_version()
     r = int(re.search(r"#define JATTS_STATS_ROWS_PER_GROUP (\d+)", hdr).group(1))
     assert r == lib.jatts_stats_rows_per_group() == _abi.STATS_ROWS_PER_GROUP == features.STATS_ROWS_PER_GROUP
 

@@ -164,7 +164,7 @@ def test_emulated_wgrad_refuses_the_six_product_code_and_falls_back_beyond_its_t
     ws = torch.empty(2 * (3 * 64 * 64 + 64), device=cuda)
     rg = rb.struct(1)
     rc = lib.jatts_conv1d_wgrad_emul(C.byref(rg), x.data_ptr(), c_in, dy.data_ptr(), n_out, c_in, n_out, 3, 1, 1, hip.F32E6, dw.data_ptr(), None,
-                                     ws.data_ptr(), None)
+                                     ws.data_ptr(), None, None)
     assert rc != 0 and b"six-product" in lib.jatts_last_error()
     assert _abi is not None
 

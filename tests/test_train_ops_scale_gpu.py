@@ -15,7 +15,8 @@ test_autograd_gpu.py reach, and which the recipe-batch tests only compare with t
 4. Scratch hygiene: tickets back at zero after every reduction launch, big and small reductions interleaved, a scratch that is too small
    refused on the host, two identical launches of every reduction on real-valued data bit-identical.
 
-Every kernel is called through its jatts_amd.hip wrapper (which registers the scratch as the trainers do); the wrappers' allocators are
+Every kernel is called through its jatts_amd.hip wrapper (which passes the device's scratch as the trainers do), section 4 also through the
+library directly with scratches of its own; the wrappers' allocators are
 swapped for patterned / canary-guarded ones where a test needs to see what a kernel did NOT write."""
 import contextlib
 import ctypes as C
@@ -572,35 +573,178 @@ def test_interleaved_reductions_do_not_leak_into_each_other(cuda, lib):
 
 
 def test_a_scratch_that_is_too_small_is_refused_on_the_host(cuda, lib):
-    """jatts_set_workspace with the minimum size, then a recipe-size LayerNorm backward: JATTS_ERR_ARG naming the bytes, nothing launched,
-    outputs untouched.  (An argument check in the launcher; the normal scratch is registered again afterwards.)"""
+    """A jatts_scratch of the minimum size, then a recipe-size LayerNorm backward: JATTS_ERR_ARG naming the bytes, nothing launched, outputs
+    untouched.  (An argument check in the launcher; the wrappers hand the library whatever hip._WS holds, and the normal scratch is put back.)"""
     from jatts_amd import _abi, hip
-    hip.col_sum(torch.ones(4, 4, device=cuda))          # the normal scratch exists and is registered
+    hip.col_sum(torch.ones(4, 4, device=cuda))          # the normal scratch exists
     key = str(cuda)
-    assert hip._WS_CURRENT[0] == key
+    normal = hip._WS[key]
+    assert normal.numel() == hip.WS_BYTES
     small = torch.zeros(TICKET_BYTES + 4096, dtype=torch.uint8, device=cuda)
     rows, dim = 24576, 384
     x, g = torch.ones(rows, dim, device=cuda), torch.ones(dim, device=cuda)
     outs = [torch.full((rows, dim), CANARY, device=cuda), torch.full((dim,), CANARY, device=cuda), torch.full((dim,), CANARY, device=cuda)]
     torch.cuda.synchronize()
+    rc = lib.jatts_layernorm_bwd(x.data_ptr(), dim, x.data_ptr(), dim, g.data_ptr(), rows, dim, 1e-5, outs[0].data_ptr(), dim,
+                                 outs[1].data_ptr(), outs[2].data_ptr(), C.byref(_abi.Scratch(small.data_ptr(), small.numel())),
+                                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    msg = lib.jatts_last_error().decode(errors="replace")
+    assert hip._WS[key] is normal                      # a direct call leaves the wrappers' scratch alone
+    hip._WS[key] = small
     try:
-        _abi.check(lib.jatts_set_workspace(small.data_ptr(), small.numel()), "jatts_set_workspace")
-        rc = lib.jatts_layernorm_bwd(x.data_ptr(), dim, x.data_ptr(), dim, g.data_ptr(), rows, dim, 1e-5, outs[0].data_ptr(), dim,
-                                     outs[1].data_ptr(), outs[2].data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        msg = lib.jatts_last_error().decode(errors="replace")
         with pytest.raises(_abi.JattsHipError, match="bytes of scratch"):       # and through the wrapper: the same refusal as an exception
             hip.layernorm_bwd(x, x, g, 1e-5)
     finally:
-        hip._WS_CURRENT[0] = None                      # the next reduction registers the normal scratch again
+        hip._WS[key] = normal
     torch.cuda.synchronize()
     assert rc == -1, rc                                # JATTS_ERR_ARG (include/jatts_hip.h)
     named = re.search(r"(\d+) bytes of scratch", msg)
-    assert named and int(named.group(1)) > small.numel() - TICKET_BYTES, msg       # a byte count, and more than was registered
+    assert named and int(named.group(1)) > small.numel() - TICKET_BYTES, msg       # a byte count, and more than was passed
     for o in outs:
         assert bool((o == CANARY).all())
     assert not bool(small.any())
     check_int(hip, "ln_dbeta", (513, 81), cuda)        # and the normal scratch works again
-    assert hip._WS_CURRENT[0] == key
+    assert hip._WS[key] is normal
+
+
+# The same reductions through the library itself, with a jatts_scratch of the test's own (include/jatts_hip.h): what the wrappers' one scratch per
+# device cannot show -- a scratch of exactly the size a launch names, and two scratches in use at once.
+DIRECT = [("ln_dbeta", (513, 81)), ("col_sum", (5, 3)), ("seq_sum", ([1, 1025, 64, 65], 65)), ("sumsq", 4097)]
+
+
+def direct_case(hip, kernel, case, dev):
+    """-> (launch(lib, scratch or None, stream) -> rc, {output: device tensor, accumulators started from their pattern}, {output: expected float64})."""
+    inp = K.make(kernel, case)
+    ref = {n: w for n, (w, _, _) in K.reference(kernel, inp).items()}
+    x = inp["x"].to(dev)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    sc = lambda scratch: None if scratch is None else C.byref(scratch)  # noqa: E731
+    st = lambda stream: C.c_void_p(stream.cuda_stream)  # noqa: E731
+    if kernel == "ln_dbeta":
+        rows, dim = case
+        dy, g = inp["dy"].to(dev), inp["gamma"].to(dev)
+        outs = {"dx": torch.full((rows, dim), CANARY, device=dev), "dg": K.pattern((dim,)).to(dev), "db": K.pattern((dim,)).to(dev)}
+        want = {"db": ref["db"] + K.pattern((dim,)).double()}
+        launch = lambda lib, scratch, stream: lib.jatts_layernorm_bwd(p(x), dim, p(dy), dim, p(g), rows, dim, 1e-5, p(outs["dx"]), dim,  # noqa: E731
+                                                                      p(outs["dg"]), p(outs["db"]), sc(scratch), st(stream))
+    elif kernel == "col_sum":
+        rows, dim = case
+        outs = {"out": K.pattern((dim,)).to(dev)}
+        want = {"out": ref["out"] + K.pattern((dim,)).double()}
+        launch = lambda lib, scratch, stream: lib.jatts_col_sum(p(x), dim, rows, dim, p(outs["out"]), sc(scratch), st(stream))  # noqa: E731
+    elif kernel == "seq_sum":
+        lens, dim = case
+        rb = hip.RaggedBatch(lens, dev)
+        outs = {"out": K.pattern((len(lens), dim)).to(dev)}
+        want = {"out": ref["out"] + K.pattern((len(lens), dim)).double()}
+        launch = lambda lib, scratch, stream: lib.jatts_seq_sum(C.byref(rb.struct()), p(x), dim, p(outs["out"]), sc(scratch), st(stream))  # noqa: E731
+    else:
+        assert kernel == "sumsq"
+        outs = {"out": torch.full((), inp["start"], dtype=torch.float64, device=dev)}
+        want = {"out": ref["out"] + inp["start"]}
+        launch = lambda lib, scratch, stream: lib.jatts_sumsq(p(x), x.numel(), p(outs["out"]), sc(scratch), st(stream))  # noqa: E731
+    return launch, outs, want
+
+
+def assert_direct(kernel, outs, want):
+    for name, w in want.items():
+        assert torch.equal(outs[name].double().cpu().reshape(w.shape), w), (kernel, name)
+
+
+@pytest.mark.parametrize("kernel,case", DIRECT, ids=[k for k, _ in DIRECT])
+def test_a_scratch_of_exactly_the_named_size_is_enough(cuda, lib, kernel, case):
+    """bytes = the tickets + the count the refusal names: accepted, exact results, nothing written behind it.  The guard half behind the
+    scratch is as large as the scratch, so a size formula that is too small fails here as an assertion, not as a store outside the buffer."""
+    from jatts_amd import _abi, hip
+    launch, outs, want = direct_case(hip, kernel, case, cuda)
+    stream = torch.cuda.current_stream()
+    start = {n: t.clone() for n, t in outs.items()}
+    probe = torch.zeros(16, device=cuda)
+    assert launch(lib, _abi.Scratch(probe.data_ptr(), 0), stream) == -1
+    named = re.search(r"(\d+) bytes of scratch", lib.jatts_last_error().decode(errors="replace"))
+    assert named, lib.jatts_last_error()
+    need = int(named.group(1))
+    assert need > 0 and need % 4 == 0
+    torch.cuda.synchronize()
+    for n, t in outs.items():
+        assert torch.equal(t, start[n]), (kernel, n, "a refused launch wrote an output")
+    buf = torch.zeros((TICKET_BYTES + 2 * need) // 4, device=cuda)
+    buf[(TICKET_BYTES + need) // 4:] = CANARY
+    torch.cuda.synchronize()
+    assert launch(lib, _abi.Scratch(buf.data_ptr(), TICKET_BYTES + need), stream) == 0, lib.jatts_last_error()
+    torch.cuda.synchronize()
+    assert_direct(kernel, outs, want)
+    assert bool((buf[(TICKET_BYTES + need) // 4:] == CANARY).all()), "a launch stored behind the scratch it was given"
+    assert not bool(buf[:TICKET_BYTES // 4].view(torch.int32).any()), "tickets left non-zero"
+
+
+def test_two_private_scratches_on_two_streams(cuda, lib):
+    """The same two integer reductions on two non-default streams, each stream with a jatts_scratch of its own and no host synchronisation in
+    between: nothing orders the streams against each other, and nothing has to."""
+    from jatts_amd import _abi, hip
+    streams = [torch.cuda.Stream(device=cuda) for _ in range(2)]
+    bufs = [torch.zeros(TICKET_BYTES + (1 << 20), dtype=torch.uint8, device=cuda) for _ in streams]
+    runs = [[(k, *direct_case(hip, k, c, cuda)) for k, c in DIRECT[:2]] for _ in streams]
+    torch.cuda.synchronize()
+    for i in range(2):                                   # launch i of stream 0, launch i of stream 1, ...
+        for s, buf, run in zip(streams, bufs, runs):
+            assert run[i][1](lib, _abi.Scratch(buf.data_ptr(), buf.numel()), s) == 0, lib.jatts_last_error()
+    torch.cuda.synchronize()
+    for buf, run in zip(bufs, runs):
+        for kernel, _, outs, want in run:
+            assert_direct(kernel, outs, want)
+        assert not bool(buf[:TICKET_BYTES].view(torch.int32).any()), "tickets left non-zero"
+
+
+def test_the_shared_scratch_is_handed_from_stream_to_stream(cuda, lib):
+    """The small members of the interleaved sequence above through the wrappers, alternating between two non-default streams with no host
+    synchronisation between the launches: the wrappers' one scratch per device changes hands at every launch, each time behind an event
+    wait (hip._scratch).  The kernels never spin on a ticket, so a missing wait would show as a wrong sum, not as a hang."""
+    from jatts_amd import hip
+    small, cs, ss = K.make("ln_dbeta", (37, 81)), K.make("col_sum", (5, 3)), K.make("seq_sum", ([1, 1025, 64, 65], 65))
+    d = lambda t: t.to(cuda)  # noqa: E731
+    dev_in = {k: {n: d(t) for n, t in inp.items() if torch.is_tensor(t)} for k, inp in (("small", small), ("cs", cs), ("ss", ss))}
+    rb = hip.RaggedBatch(ss["lens"], cuda)
+    pats = {shape: K.pattern(shape).to(cuda) for shape in ((81,), (3,), (4, 65))}
+    hip.col_sum(dev_in["cs"]["x"])                       # the scratch exists
+    torch.cuda.synchronize()
+    ops = [("layernorm 37x81 dbeta", "ln_dbeta", small, "db", lambda: hip.layernorm_bwd(dev_in["small"]["x"], dev_in["small"]["dy"], dev_in["small"]["gamma"], 1e-5)[2]),
+           ("col_sum 5x3", "col_sum", cs, "out", lambda: hip.col_sum(dev_in["cs"]["x"])),
+           ("seq_sum", "seq_sum", ss, "out", lambda: hip.seq_sum(rb, dev_in["ss"]["x"]))]
+    streams = [torch.cuda.Stream(device=cuda) for _ in range(2)]
+    got = []
+    with patterned_accumulators(hip, prebuilt=pats):
+        for i in range(2 * len(ops)):                    # six launches: every op runs once on each stream
+            with torch.cuda.stream(streams[i % 2]):
+                got.append((ops[i % len(ops)], ops[i % len(ops)][4]()))
+    torch.cuda.synchronize()
+    tickets_clear(hip, cuda)
+    assert hip._WS_OWNER[str(cuda)][0] == streams[1].cuda_stream
+    for (name, kernel, inp, out, _), t in got:
+        want = K.reference(kernel, inp)[out][0]
+        assert torch.equal(t.double().cpu(), want + K.pattern(want.shape).double()), name
+
+
+def test_a_null_scratch_where_nothing_reduces(cuda, lib):
+    """LayerNorm backward without the parameter gradients, the Q|K|V split without position biases: no cross-workgroup sum, scratch = NULL."""
+    from jatts_amd import hip
+    inp = K.make("ln_dbeta", (37, 81))
+    x, dy, g = (inp[n].to(cuda) for n in ("x", "dy", "gamma"))
+    dx = torch.full((37, 81), CANARY, device=cuda)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.jatts_layernorm_bwd(x.data_ptr(), 81, dy.data_ptr(), 81, g.data_ptr(), 37, 81, 1e-5, dx.data_ptr(), 81, None, None, None, stream) == 0, \
+        lib.jatts_last_error()
+    dx_full, _, _ = hip.layernorm_bwd(x, dy, g, 1e-5)
+    torch.cuda.synchronize()
+    assert torch.equal(dx, dx_full) and bool((dx != CANARY).all())
+    q = K.make("qkv_split_bwd", (1, 513, 3, 27))
+    dqu, dk, dvv = (q[n].to(cuda) for n in ("dqu", "dk", "dvv"))
+    dqkv = torch.full((513, 3 * 81), CANARY, device=cuda)
+    assert lib.jatts_qkv_split_bwd(dqu.data_ptr(), None, dk.data_ptr(), dvv.data_ptr(), 1, 513, 3, 27, dqkv.data_ptr(), None, None, None, stream) == 0, \
+        lib.jatts_last_error()
+    torch.cuda.synchronize()
+    rows = lambda t: t.permute(0, 2, 1, 3).reshape(513, 81)  # noqa: E731
+    assert torch.equal(dqkv.cpu(), torch.cat([rows(q["dqu"]), rows(q["dk"]), rows(q["dvv"])], dim=1))
 
 
 def _repeat_cases(hip, dev):
