@@ -144,23 +144,18 @@ def viterbi_decode(log_p_attn, text_lengths, feats_lengths, k=None):
     return ds, bin_loss.float()
 
 
-_SEL_CACHE = {}
+_SELECTIONS = hip.DeviceCache("alignments.frame_token_indices", max_entries=64, register=True)
 
 
 def frame_token_indices(text_lengths, feats_lengths, Tt, Tf, device):
     """Row indices of the valid tokens / frames of a padded batch, as device int64 tensors (one host -> device copy each; build them
     BEFORE queueing GPU work: a mid-forward torch.tensor(..., device=...) stalls the host behind everything already queued)."""
-    key = (tuple(int(n) for n in text_lengths), tuple(int(n) for n in feats_lengths), int(Tt), int(Tf), str(device))
-    hit = _SEL_CACHE.get(key)          # constant per length bucket: building two 4 k / 25 k-element Python lists costs ms per step
-    if hit is None:
-        tsel = hip.h2d([b * Tt + i for b, n in enumerate(key[0]) for i in range(n)], torch.int64, device)
-        fsel = hip.h2d([b * Tf + t for b, n in enumerate(key[1]) for t in range(n)], torch.int64, device)
-        if len(_SEL_CACHE) >= 64:
-            _SEL_CACHE.pop(next(iter(_SEL_CACHE)))
-        _SEL_CACHE[key] = hit = (tsel, fsel)
-    hip.keep(hit[0])          # (a graph being captured pins them: the cache evicts)
-    hip.keep(hit[1])
-    return hit
+    key = (tuple(int(n) for n in text_lengths), tuple(int(n) for n in feats_lengths), int(Tt), int(Tf))
+
+    def build():                       # constant per length bucket: building two 4 k / 25 k-element Python lists costs ms per step
+        return (hip.upload([b * Tt + i for b, n in enumerate(key[0]) for i in range(n)], torch.int64, device),
+                hip.upload([b * Tf + t for b, n in enumerate(key[1]) for t in range(n)], torch.int64, device))
+    return _SELECTIONS.get(key, device, build)
 
 
 @torch.no_grad()

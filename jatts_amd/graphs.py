@@ -8,13 +8,16 @@ memory pool: plumbing, like the stream and the allocator everywhere else -- and 
 the same kernels in the same order on the same arithmetic, bit-identical to the eager launches (tests/test_graph_gpu.py).
 
 Rules (tests/test_graph_policy_cpu.py):
-  * a signature's FIRST sight runs eagerly -- it fills the bounded host-to-device caches (ragged geometry, positional tables) that a
-    capture may not upload into -- its SECOND sight captures, later ones replay;
+  * a signature's FIRST sight runs eagerly -- it fills the bounded caches of device constants (hip.DeviceCache: uploads, ragged geometry,
+    index lists, positional tables, priors), every one of which refuses a new entry during a capture -- its SECOND sight captures, later
+    ones replay;
   * signatures seen once and never again are bounded: at `max_seen` entries the oldest never-captured ones are dropped;
   * least-recently-used graphs are dropped beyond `max_graphs` (each owns one call's activations); their next sight captures again;
-  * every cached device tensor handed out during a capture is pinned by the graph's record (hip.keep_begin), the caches may evict.  Only
-    those: a tensor the caller looked up BEFORE the call is not recorded and is freed under the graph once the bounded caches drop it, so
-    a captured function builds its own ragged geometry from the lengths (RaggedBatch(lens, dev) inside `fn`: a cache hit, recorded);
+  * every cached device tensor handed out during a capture is pinned by the graph's record (hip.keep_begin), the caches may evict.
+    hip.DeviceCache.get is the one place that rule lives (with the bounds, the device key, the ordering behind an upload made on another
+    stream and the refusal above); a new cache is an instance of it.  Only what is handed out DURING the capture is pinned: a tensor the
+    caller looked up BEFORE the call is not recorded and is freed under the graph once the bounded caches drop it, so a captured function
+    builds its own ragged geometry from the lengths (RaggedBatch(lens, dev) inside `fn`: a cache hit, recorded);
   * the key holds everything the launch sequence and its cached operands depend on -- besides the shapes, the positional table length of
     the conformer stacks (ConformerRunner.table_len), which regrows for good after a longer input and changes the table's values;
   * whatever leaves a capture as an exception marks the signature eager-only for good.  GraphCache logs it and answers the call by eager

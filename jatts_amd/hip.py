@@ -214,9 +214,9 @@ _KEEP = [None]        # while a graph is being captured (graphs.capture): every 
 
 
 def keep_begin():
-    """Start recording the cached device tensors handed out from here on (hip.h2d, RaggedBatch geometry, the models' per-length tables):
-    a captured graph reads them at their addresses for as long as it is replayed, while the caches are bounded and evict -- the capture's
-    owner keeps the returned list alive next to the graph (jatts_amd.graphs.capture, the only caller)."""
+    """Start recording the cached device tensors handed out from here on (every DeviceCache: uploads, ragged geometry, the models' per-length
+    tables): a captured graph reads them at their addresses for as long as it is replayed, while the caches are bounded and evict -- the
+    capture's owner keeps the returned list alive next to the graph (jatts_amd.graphs.capture, the only caller)."""
     _KEEP[0] = []
     return _KEEP[0]
 
@@ -226,50 +226,135 @@ def keep_end():
 
 
 def keep(t):
-    """Called by every cache that hands out a device tensor (hit or miss); returns t."""
+    """Record t for the capture in progress, if there is one; returns t.  DeviceCache.get calls it for everything it hands out."""
     if _KEEP[0] is not None and t is not None:
         _KEEP[0].append(t)
     return t
 
 
-def h2d(values, dtype, device):
-    """Small host list -> device tensor WITHOUT stalling the host: staged through pinned memory and copied asynchronously on the
+_DEVICES = {}         # a spelling that names its index ("cuda:0", torch.device("cuda", 0), "cpu") -> the torch.device
+
+
+def canonical_device(device):
+    """The ONE spelling of a device: a torch.device that carries its index on the GPU ("cuda" and torch.device("cuda") mean the current
+    device, now)."""
+    dev = _DEVICES.get(device)
+    if dev is None:
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            return torch.device("cuda", torch.cuda.current_device())
+        _DEVICES[device] = dev
+    return dev
+
+
+_DEVICE_CACHES = []
+
+
+class DeviceCache:
+    """A bounded cache of small device constants that depend only on lengths (uploads, ragged offsets, index lists, positional tables,
+    priors), and the one place the rules for such tensors live (jatts_amd/graphs.py relies on them):
+      * the key holds the device, spelled one way (canonical_device);
+      * bounded by entries and / or device bytes; the old end is evicted, never the entry just inserted; `lru` moves a hit to the young end;
+      * an entry remembers the stream it was built on and an event behind the build: another stream that hits it first waits for the event;
+      * a miss while the current stream is capturing raises -- nothing may be uploaded or built into a graph;
+      * everything handed out, hit or miss, goes through keep(): a capture pins what it reads, the cache may evict it.
+    On a device that is not a GPU only the bounds and keep() apply."""
+
+    def __init__(self, name, max_entries=None, max_bytes=None, lru=False, register=False):
+        self.name, self.max_entries, self.max_bytes, self.lru = name, max_entries, max_bytes, lru
+        self._entries = collections.OrderedDict()     # (key, device) -> [value, its tensors, their bytes, event or None once complete, stream handle]; old end first
+        self._bytes = 0
+        if register:                                  # the module-level caches (device_caches); one owned by an object dies with it
+            _DEVICE_CACHES.append(self)
+
+    def __len__(self):
+        return len(self._entries)
+
+    def clear(self):
+        self._entries.clear()
+        self._bytes = 0
+
+    def get(self, key, device, build):
+        """The value of (key, device); build() makes it on a miss: a tensor, or nested tuples / lists of tensors, None, plain values and
+        objects that own tensors."""
+        dev = canonical_device(device)
+        key = (key, dev)
+        e = self._entries.get(key)
+        if e is not None:
+            if self.lru:
+                self._entries.move_to_end(key)
+            if e[3] is not None and not torch.cuda.is_current_stream_capturing():
+                if e[3].query():
+                    e[3] = None                       # complete: every stream may read it from now on
+                elif e[4] != torch.cuda.current_stream(dev).cuda_stream:
+                    torch.cuda.current_stream(dev).wait_event(e[3])
+        else:
+            cuda = dev.type == "cuda"
+            if cuda and torch.cuda.is_current_stream_capturing():
+                raise _abi.JattsHipError(f"{self.name}: a new entry while a graph is being captured: run the step once outside the capture first")
+            value = build()
+            leaves = _leaves(value, [])
+            e = [value, leaves, sum(t.numel() * t.element_size() for t in leaves if torch.is_tensor(t)), None, None]
+            if cuda:
+                stream = torch.cuda.current_stream(dev)
+                e[3], e[4] = torch.cuda.Event(), stream.cuda_stream
+                e[3].record(stream)
+            self._entries[key] = e
+            self._bytes += e[2]
+            while len(self._entries) > 1 and ((self.max_entries is not None and len(self._entries) > self.max_entries)
+                                              or (self.max_bytes is not None and self._bytes > self.max_bytes)):
+                self._bytes -= self._entries.popitem(last=False)[1][2]
+        if _KEEP[0] is not None:
+            for t in e[1]:
+                keep(t)
+        return e[0]
+
+
+def _leaves(value, out):
+    """Everything in a cached value that can own device memory (tensors, prepared operands), depth first."""
+    if isinstance(value, (list, tuple)):
+        for v in value:
+            _leaves(v, out)
+    elif value is not None and not isinstance(value, (int, float, str)):
+        out.append(value)
+    return out
+
+
+def device_caches():
+    """The package's module-level DeviceCaches."""
+    return list(_DEVICE_CACHES)
+
+
+def clear_device_caches():
+    for c in _DEVICE_CACHES:
+        c.clear()
+
+
+def upload(values, dtype, device):
+    """Host values -> a NEW device tensor WITHOUT stalling the host: staged through pinned memory and copied asynchronously on the
     current stream.  torch.tensor(values, device=...) copies from pageable memory, which blocks the host until everything already
-    queued on the stream has run -- one pipeline drain per call in the middle of a forward pass."""
-    dev = torch.device(device)
+    queued on the stream has run -- one pipeline drain per call in the middle of a forward pass.  Refused under a graph capture: the
+    graph would hold a copy from a host buffer that is gone."""
+    dev = canonical_device(device)
     if dev.type != "cuda":
         return torch.tensor(values, dtype=dtype, device=dev)
-    # small length-derived arrays repeat from step to step (same bucket of lengths): cached per (values, dtype, device), which also makes
-    # a training step capturable -- a cache hit issues no copy, so a captured graph never holds a memcpy from a host buffer that is gone.
-    # LRU, bounded by BYTES (device bytes + the key tuple's ~8 x that on the host): a long decode run produces a new key per batch.
-    key = None
-    if isinstance(values, (list, tuple)) and len(values) <= 65536 and all(isinstance(v, (int, float, bool)) for v in values[:1] + values[-1:]):
-        key = (tuple(values), dtype, dev.index if dev.index is not None else torch.cuda.current_device())
-        hit = _H2D_CACHE.get(key)
-        if hit is not None:
-            _H2D_CACHE.move_to_end(key)
-            if hit[2] != torch.cuda.current_stream().cuda_stream and not torch.cuda.is_current_stream_capturing() and not hit[1].query():
-                torch.cuda.current_stream().wait_event(hit[1])
-            return keep(hit[0])
     if torch.cuda.is_current_stream_capturing():
         raise _abi.JattsHipError("h2d of new values while a graph is being captured: run the step once outside the capture first")
-    t = torch.tensor(values, dtype=dtype).pin_memory().to(dev, non_blocking=True)
-    if key is not None:
-        ev = torch.cuda.Event()
-        ev.record()
-        _H2D_CACHE[key] = (t, ev, torch.cuda.current_stream().cuda_stream)
-        _H2D_BYTES[0] += t.numel() * t.element_size()
-        while _H2D_BYTES[0] > _H2D_CACHE_MAX_BYTES and len(_H2D_CACHE) > 1:
-            _, old = _H2D_CACHE.popitem(last=False)
-            _H2D_BYTES[0] -= old[0].numel() * old[0].element_size()
-    return keep(t)
+    return torch.tensor(values, dtype=dtype).pin_memory().to(dev, non_blocking=True)
 
 
-_H2D_CACHE = collections.OrderedDict()       # (values, dtype, device) -> (tensor, upload-complete event, stream); least recently used first
-_H2D_BYTES = [0]
-_H2D_CACHE_MAX_BYTES = 8 << 20               # device bytes; the host-side key tuples cost about 8x that
-_GEOM_CACHE = {}      # (lens, device) -> (cu tensor, upload-complete event); insertion-ordered, oldest evicted
-_GEOM_CACHE_MAX = 512
+def h2d(values, dtype, device):
+    """upload() behind a cache.  Small length-derived lists repeat from step to step (same bucket of lengths): cached per (values, dtype,
+    device), which also makes a training step capturable -- a hit issues no copy.  LRU, bounded by BYTES: a long decode run produces a
+    new key per batch.  Anything else (long lists, arrays, tensors) is uploaded afresh."""
+    dev = canonical_device(device)
+    if dev.type == "cuda" and isinstance(values, (list, tuple)) and len(values) <= 65536 and all(isinstance(v, (int, float, bool)) for v in values[:1] + values[-1:]):
+        return _UPLOADS.get((tuple(values), dtype), dev, lambda: upload(values, dtype, dev))
+    return keep(upload(values, dtype, dev))
+
+
+_UPLOADS = DeviceCache("hip.h2d", max_bytes=8 << 20, lru=True, register=True)      # device bytes; the host-side key tuples cost about 8x that
+_GEOMETRY = DeviceCache("RaggedBatch geometry", max_entries=512, register=True)
 
 
 def exclusive_scan(lens):
@@ -293,22 +378,11 @@ class RaggedBatch:
         self.n_seq = len(self.lens)
         self.max_len = max(self.lens) if self.lens else 0
         self.device = device
-        dev = torch.device(device)
+        dev = canonical_device(device)
         if dev.type != "cuda":
-            self.cu = torch.tensor(cu, dtype=torch.int32, device=dev)
-            return
-        key = (tuple(self.lens), dev.index if dev.index is not None else torch.cuda.current_device())
-        hit = _GEOM_CACHE.get(key)
-        if hit is None:
-            t = h2d(cu, torch.int32, dev)
-            ev = torch.cuda.Event()
-            ev.record()
-            if len(_GEOM_CACHE) >= _GEOM_CACHE_MAX:
-                _GEOM_CACHE.pop(next(iter(_GEOM_CACHE)))
-            _GEOM_CACHE[key] = hit = (t, ev, torch.cuda.current_stream().cuda_stream)
-        elif hit[2] != torch.cuda.current_stream().cuda_stream and not torch.cuda.is_current_stream_capturing() and not hit[1].query():
-            torch.cuda.current_stream().wait_event(hit[1])     # uploaded on another stream and still in flight
-        self.cu = keep(hit[0])
+            self.cu = upload(cu, torch.int32, dev)
+        else:
+            self.cu = _GEOMETRY.get(tuple(self.lens), dev, lambda: upload(cu, torch.int32, dev))
 
     def struct(self, len_mul=1):
         if _RAGGED_1D and self.n_seq > 1 and min(self.lens) != self.max_len:     # a ragged batch: 1-D grids over its real tiles (jatts_ragged.host_lens)

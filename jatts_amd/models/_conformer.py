@@ -132,7 +132,7 @@ class ConformerRunner:
         if (prefix + "after_norm.weight") in sd:
             self.after_norm = (f32(g("after_norm.weight")), f32(g("after_norm.bias")))
         self.pe_len = PE_TABLE_LEN   # sticky, like the reference's regrown buffer (extend_pe)
-        self._pos_cache = {}         # cap -> per-layer (per-head packed P, cv)
+        self._pos_cache = hip.DeviceCache("ConformerRunner._pos", max_entries=8)         # cap -> per-layer (per-head packed P, cv)
 
     def table_len(self, t_max):
         """Length of the positional table a run over t_max positions uses: the values of the legacy table depend on it, so it belongs to the
@@ -145,8 +145,9 @@ class ConformerRunner:
             self.pe_len = t_max
             self._pos_cache.clear()
         cap = hip.round_up(t_max, 128)
-        if cap in self._pos_cache:
-            return cap, hip.keep(self._pos_cache[cap])      # (a capturing graph pins what it was handed: the cache evicts)
+        return cap, self._pos_cache.get(cap, self.device, lambda: self._pos_build(cap))
+
+    def _pos_build(self, cap):
         if self.rel_style == "new":
             pe = rel_pos_table_new(cap, self.A)          # (2cap-1, A)
         else:
@@ -166,10 +167,7 @@ class ConformerRunner:
             # per-head weight operand of the BD GEMM (n = position m, contraction d_k): pure re-layout
             heads = [hip.operand(self.operand, P[:, h * self.dk:(h + 1) * self.dk].float().unsqueeze(-1)) for h in range(self.H)]
             per_layer.append((heads, cv))
-        if len(self._pos_cache) >= 8:
-            self._pos_cache.pop(next(iter(self._pos_cache)))
-        self._pos_cache[cap] = per_layer
-        return cap, hip.keep(per_layer)
+        return per_layer
 
     def _ffn(self, rb, x, ln, ff, scale):
         xn = hip.layernorm(x, ln[0], ln[1], self.dtype, LN_EPS)

@@ -87,20 +87,14 @@ def spk_integrate(c, model, hs, spembs, rb, rbs):
     return A.AddSeqVector.apply(A.Conv1dFunction.apply(hs, w[:, :Ad].unsqueeze(-1).contiguous(), None, rb, 1, 0), vec, rb)
 
 
-_POS_TABLES = {}
+_POS_TABLES = hip.DeviceCache("fastspeech2_train._pos_table", max_entries=64, register=True)
 
 
 def _pos_table(rel_style, T, Ad, device):
     """rel_style "new": RelPositionalEncoding's (2T-1, A) table (positional_encoding.py:265-309); "legacy": pe[:, :T] of the reversed table
     (positional_encoding.py:221-235).  Constant per (style, T, A): kept on the device (also what makes the step capturable)."""
-    key = (rel_style, T, Ad, str(device))
-    t = _POS_TABLES.get(key)
-    if t is None:
-        t = (rel_pos_table_new(T, Ad) if rel_style == "new" else legacy_rel_pos_table(T, Ad, max(PE_TABLE_LEN, T))).to(device)
-        if len(_POS_TABLES) >= 64:
-            _POS_TABLES.pop(next(iter(_POS_TABLES)))
-        _POS_TABLES[key] = t
-    return hip.keep(t)        # (a graph being captured pins it: the cache evicts)
+    return _POS_TABLES.get((rel_style, T, Ad), device, lambda: (
+        rel_pos_table_new(T, Ad) if rel_style == "new" else legacy_rel_pos_table(T, Ad, max(PE_TABLE_LEN, T))).to(device))
 
 
 def _conformer(c, prefix, x, rb, kv, H, rates, rel_style="legacy"):

@@ -207,20 +207,13 @@ def beta_binomial_prior(ilens, olens, w=1.0):
     return out
 
 
-_PRIOR_DEV = {}
+_PRIOR_DEV = hip.DeviceCache("matchatts_train.beta_binomial_prior_dev", max_entries=16, register=True)
 
 
 def beta_binomial_prior_dev(ilens, olens, device):
     """beta_binomial_prior on the device, cached per (ilens, olens, device): the (B, To, Tm) tensor is 12.6 MB at the recipes' batch -- assembling
     it on the host and uploading it from pageable memory cost ~10 ms of every MAS-phase step."""
-    key = (tuple(ilens), tuple(olens), str(device))
-    t = _PRIOR_DEV.get(key)
-    if t is None:
-        t = beta_binomial_prior(list(ilens), list(olens)).to(device)
-        if len(_PRIOR_DEV) >= 16:
-            _PRIOR_DEV.pop(next(iter(_PRIOR_DEV)))
-        _PRIOR_DEV[key] = t
-    return hip.keep(t)        # (a graph being captured pins it: the cache evicts)
+    return _PRIOR_DEV.get((tuple(ilens), tuple(olens)), device, lambda: beta_binomial_prior(list(ilens), list(olens)).to(device))
 
 
 def criterion(ret, durations, ilens, duration_loss=True, olens=None, forward_sum=False, bin_loss=False, lambda_align=2.0):

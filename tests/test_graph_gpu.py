@@ -254,11 +254,11 @@ def test_graph_replay_survives_upload_cache_churn(cuda, lib, monkeypatch):
     _assert_geometry_pinned(caps, [fgc, vgc], 3)
     ref_f = _eager(lambda: [m.inference_batch([t], durations=[d])["feat_gen"] for t in texts[2:]])
     ref_v = _eager(lambda: [v.decode(c)[0] for c in mels[2:]])
-    for n in range(3 * hip._GEOM_CACHE_MAX // 2):        # fresh geometries: the oldest entries are evicted
+    (geometry,) = [c for c in hip.device_caches() if c.name == "RaggedBatch geometry"]
+    for n in range(3 * geometry.max_entries // 2):       # fresh geometries: the oldest entries are evicted
         hip.RaggedBatch([100003 + n], cuda)
-    hip._H2D_CACHE.clear()
-    hip._H2D_BYTES[0] = 0
-    hip._GEOM_CACHE.clear()
+    assert len(geometry) == geometry.max_entries
+    hip.clear_device_caches()
     pygc.collect()
     torch.cuda.synchronize()
     fill = [torch.zeros(128, dtype=torch.int32, device=cuda) for _ in range(8192)]    # 512-byte blocks: the size class of a freed geometry

@@ -853,10 +853,8 @@ def test_captured_graph_pins_its_cached_inputs_and_stages_scalars_per_step(cuda,
     # evict everything the capture was handed
     for i in range(700):
         hip.RaggedBatch([3 + i, 5], cuda)
-    hip._H2D_CACHE.clear()
-    hip._H2D_BYTES[0] = 0
-    hip._GEOM_CACHE.clear()
-    ft._POS_TABLES.clear()
+    hip.clear_device_caches()
+    assert all(len(c) == 0 for c in hip.device_caches()) and ft._POS_TABLES in hip.device_caches()
     gc.collect()
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
