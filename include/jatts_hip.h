@@ -970,6 +970,52 @@ int jatts_dtw_path_stats(int32_t n_pairs, const int64_t* tab, const int32_t* pat
                          const float* a, int32_t lda, const float* b, int32_t ldb, int32_t dim, const float* x, const float* y,
                          double* out, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Griffin-Lim phase reconstruction (additive to ABI 8): the waveform of a magnitude spectrogram where a config has no
+ * vocoder (the reference's Spectrogram2Waveform, tts_decode.py:190-200, tts_train.py:316-325, whose module does not exist there).  The
+ * arithmetic is a definition of this project's own, pinned on a float64 restatement (tests/griffinlim_reference.py); parity with
+ * librosa.griffinlim and ESPnet's logmel2linear is UNPINNED.  With S >= 0 (rows, n_bins), P0 unit phases, beta = momentum / (1 + momentum):
+ *   X_0 = S P0, C_-1 = 0;  n_iter times  x = ISTFT(X), C = STFT(x), A = C - beta C_prev, X = S A / (|A| + 2^-126);  y = ISTFT(X).
+ * STFT: centred frames, ZEROS outside [0, L) (torch.stft(center=True, pad_mode="constant")), L = (T - 1) hop, exactly T frames.
+ * ISTFT: y[n] = sum_t w[p - t hop] irfft(X_t)[p - t hop] / sum_t w^2[p - t hop], p = n + n_fft / 2, 0 <= n < L
+ * (torch.istft(center=True, length=L)); the imaginary parts of the DC and Nyquist bins are ignored.  One frame gives no sample.
+ * Shared geometry: nbp = n_bins rounded up to 32; a spectrum row is [re 0..nbp) | im 0..nbp), pitch ldx = 2 nbp exactly (what the tables
+ * are built for), padding bins zero; the waveform of utterance b starts at cu_rows[b] * hop (the frame layout: rows * hop floats, the last
+ * hop of every utterance unused).  host_frames (HOST, n_seq): the frame counts, read at launch time only.  Both contractions are exact f32
+ * with the fixed two-level order of jatts_stft_mag (a chain per 64 table rows, chains added in order; no atomics): an utterance's bits
+ * depend on its own rows and the tables only.  JATTS_ERR_ARG: a null pointer, n_fft > 2048 or not a multiple of 64, hop < 1 or hop > n_fft,
+ * ldx != 2 nbp, a table of another geometry, an utterance without a frame, host_frames that disagree with rg_frames, aliased buffers.
+ * JATTS_ERR_UNSUPPORTED: ceil(n_fft / hop) > 64, more than 65535 utterances, 2^31 floats or more in a buffer.  Zero rows: JATTS_OK, no launch.
+ * ------------------------------------------------------------------------------- */
+/* One half-iteration: C = STFT(x) with table = jatts_amd.features.dft_table ([n_fft][2 nbp]), and in the epilogue, per (frame, bin < n_bins),
+ *   ar = fmaf(-beta, Cp.re, C.re), ai likewise, q = S / (sqrtf(fmaf(ar, ar, ai * ai)) + 2^-126), x_next = (q ar, q ai), c_prev = C;
+ * padding bins of x_next and c_prev are written zero (where |A| < 2^-60, A and 2^-126 are first scaled by 2^96, exactly, so that the squares
+ * stay normal numbers: the same quotient).  Neither the frame matrix nor A reaches memory.  beta in [0, 1).
+ * Tested to: |dC| <= 1.01 K 2^-24 sum |w x| + K 2^-149 per component (K = n_fft) against float64 on the same f32 inputs, x_next within the
+ * bound tests/test_griffinlim_gpu.py derives from it. */
+int jatts_gl_stft_project(const jatts_ragged* rg_frames, const int32_t* host_frames, const float* x, const float* table, int32_t n_fft,
+                          int32_t hop, const float* S, int32_t lds, float beta, float* c_prev, float* x_next, int32_t ldx, void* stream);
+/* y = ISTFT(X) as one span contraction per output row m (n + n_fft / 2 = m hop + r, J = ceil(n_fft / hop)):
+ *   num[m][r] = sum_{i < J} sum_{k < 2 nbp} Xflat[m - J + 1 + i][k] * table[i * 2 nbp + k][r],  zeros where the row lies outside [0, T),
+ * table: [J * 2 nbp][hopp] f32, hopp = hop rounded up to 32, entry (i, k, r) = c_k cos(2 pi k q / n_fft) w[q] / n_fft (real plane) or
+ * -c_k sin(..) w[q] / n_fft (imaginary plane) with q = (J - 1 - i) hop + r, 0 where q >= n_fft or in padding, c_k = 1 at DC and Nyquist,
+ * 2 elsewhere (jatts_amd.vocoder.griffin_lim.istft_table; table_rows / table_cols repeat its shape).  y[n] = num * renv[j_lo][j_hi][r],
+ * renv: [J][J][hopp] f32 = 1 / sum_{j_lo <= j <= j_hi} w^2[j hop + r] in float64 rounded once (istft_envelope), (j_lo, j_hi) =
+ * (max(0, m - T + 1), min(J - 1, m)): the frames that exist.  packed = 0: utterance b at cu_rows[b] * hop (the frame layout; its last hop
+ * floats are not written); packed = 1: at (cu_rows[b] - b) * hop, the utterances back to back.  Nothing outside [0, L) of an utterance is
+ * written.  Tested to: (1.01 K 2^-24 sum |table X| + K 2^-149) / env + 2^-24 |y|, K = J * 2 nbp. */
+int jatts_gl_istft(const jatts_ragged* rg_frames, const int32_t* host_frames, const float* X, int32_t ldx, const float* table,
+                   int32_t table_rows, int32_t table_cols, const float* renv, int32_t n_fft, int32_t hop, int32_t packed, float* y,
+                   void* stream);
+/* out[row][k] = base ** fmaf(c[row][k], scale[k], mean[k]) for k < n_mels, 0 up to ldo: de-normalised log-mel features back to the linear mel
+ * domain.  log_base: 0 = e, 2 or 10.  The power is taken in double and rounded to f32 once (tested to 1 ulp of the f32 result). */
+int jatts_gl_exp(const float* c, int32_t ldc, int32_t n_mels, int64_t rows, const float* scale, const float* mean, int32_t log_base,
+                 float* out, int32_t ldo, void* stream);
+/* out[row][k] = max(eps, lin[row][k]) for k < n_bins, 0 up to ldo (exact): the floor behind the pseudo-inverse mel projection. */
+int jatts_gl_floor(const float* lin, int32_t ldl, int32_t n_bins, int64_t rows, float eps, float* out, int32_t ldo, void* stream);
+/* X_0 = S P0: X[row] = [S re(p0) | S im(p0)] (one f32 multiply each), padding bins zero.  p0: complex64 (rows, n_bins), interleaved. */
+int jatts_gl_init(const float* S, int32_t lds, const float* p0, int32_t n_fft, int64_t rows, float* X, int32_t ldx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

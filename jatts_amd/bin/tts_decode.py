@@ -216,14 +216,17 @@ def main(argv=None):
     logging.info(f"Loaded model parameters from {args.checkpoint}.")
 
     stats = read_stats(args.stats, config["out_feat_type"])                # tts_decode.py:160-164
-    if not config.get("vocoder", False):
-        raise NotImplementedError("Griffin-Lim fallback (no vocoder) is outside the HIP path")
-    vcfg = config["vocoder"]
-    if vcfg.get("vocoder_type", "") not in ("", "hifigan", "parallel_wavegan"):
+    vcfg = config.get("vocoder") or {}
+    if vcfg.get("vocoder_type", "") not in ("", "hifigan", "parallel_wavegan", "griffin_lim"):
         raise NotImplementedError(f"vocoder_type {vcfg.get('vocoder_type')} is not on the HIP path")
-    vocoder = Vocoder(vcfg["checkpoint"], vcfg["config"], vcfg["stats"], device, trg_stats=stats)
+    if not vcfg or vcfg.get("vocoder_type") == "griffin_lim":               # tts_decode.py:190-200: no vocoder, Griffin-Lim
+        from jatts_amd.vocoder import Spectrogram2Waveform
+        vocoder = Spectrogram2Waveform.from_config(config, stats, device)
+        logging.info(f"No vocoder: Griffin-Lim with {vocoder.gl.n_iter} iterations.")
+    else:
+        vocoder = Vocoder(vcfg["checkpoint"], vcfg["config"], vcfg["stats"], device, trg_stats=stats)
     vocoder.set_precision(args.precision)
-    hop = vocoder.model.hop
+    hop = vocoder.hop
     uses_spk = "spkemb" in config.get("feat_list", [])
     kw = {}
     if config["model_type"] in ("MatchaTTS", "MatchaTTS_MAS"):              # tts_decode.py:217-226

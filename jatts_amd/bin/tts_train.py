@@ -122,7 +122,7 @@ def main(argv=None):
     elif vcfg:
         logging.info("The vocoder's files do not exist: intermediate waveforms are skipped.")
     else:
-        logging.info("No vocoder in the config: intermediate waveforms are skipped (no Griffin-Lim fallback).")
+        vocoder = training.griffin_lim_fallback(config, lambda: read_stats(args.stats, config["out_feat_type"]), device)
 
     trainer = trainer_class(model, precision=args.precision, attention=args.attention_precision, capture_graph=False, **kw)
     logging.info(model)

@@ -1543,6 +1543,80 @@ def wave_gain_peak(cu, n_seq, y, gain):
     return peak
 
 
+# ---- Griffin-Lim (csrc/griffinlim.hip; host layer: jatts_amd/vocoder/griffin_lim.py)
+def _gl_frames(name, rb):
+    if rb.n_seq and min(rb.lens) < 1:
+        raise ValueError(f"{name}: every utterance needs at least one frame")
+    return (C.c_int32 * max(rb.n_seq, 1))(*rb.lens)
+
+
+def gl_stft_project(rb, x, table, n_fft, hop, S, beta, c_prev, x_next):
+    """jatts_gl_stft_project: one half-iteration, in place on ``c_prev`` and ``x_next`` (both f32 (rows, 2 * nbp)).  ``x``: f32 of at least
+    rows * hop samples in the frame layout (utterance b at cu[b] * hop), ``table``: features.dft_table, ``S``: f32 (rows, lds >= n_bins)."""
+    lib = _abi.load()
+    _f32d("gl_stft_project", "contiguous float32 device buffers", x, table, S, c_prev, x_next, dims=(1, 2, 2, 2, 2))
+    nbp = round_up(n_fft // 2 + 1, 32)
+    if (x.numel() < rb.total * hop or S.shape[0] < rb.total or c_prev.shape[0] < rb.total or x_next.shape[0] < rb.total
+            or c_prev.shape[1] != x_next.shape[1]):
+        raise ValueError("gl_stft_project: a buffer is smaller than the frame geometry")
+    if 64 <= n_fft <= 2048 and table.numel() != n_fft * 2 * nbp:
+        raise ValueError("gl_stft_project: table is not (n_fft, 2 * round_up(n_bins, 32))")
+    ns, rg = _gl_frames("gl_stft_project", rb), rb.struct()
+    _abi.check(lib.jatts_gl_stft_project(C.byref(rg), ns, x.data_ptr(), table.data_ptr(), n_fft, hop, S.data_ptr(), S.shape[1], float(beta),
+                                         c_prev.data_ptr(), x_next.data_ptr(), x_next.shape[1], _stream()), "jatts_gl_stft_project")
+    _count(2.0 * n_fft * 2 * nbp * rb.total)
+
+
+def gl_istft(rb, X, table, renv, n_fft, hop, y, packed=False):
+    """jatts_gl_istft: ``X`` f32 (rows, 2 * nbp) -> ``y`` (f32, in place): utterance b's (T_b - 1) * hop samples at cu[b] * hop (the frame
+    layout, at least rows * hop floats) or, ``packed``, back to back (at least (rows - n_seq) * hop floats).  ``table`` / ``renv``:
+    vocoder.griffin_lim.istft_table / istft_envelope."""
+    lib = _abi.load()
+    _f32d("gl_istft", "contiguous float32 device buffers", X, table, renv, y, dims=(2, 2, 3, 1))
+    if X.shape[0] < rb.total or y.numel() < (rb.total - (rb.n_seq if packed else 0)) * hop:
+        raise ValueError("gl_istft: a buffer is smaller than the frame geometry")
+    j = -(-n_fft // max(hop, 1))
+    if hop >= 1 and tuple(renv.shape) != (j, j, table.shape[1]):
+        raise ValueError("gl_istft: the envelope is not (J, J, round_up(hop, 32))")
+    ns, rg = _gl_frames("gl_istft", rb), rb.struct()
+    _abi.check(lib.jatts_gl_istft(C.byref(rg), ns, X.data_ptr(), X.shape[1], table.data_ptr(), table.shape[0], table.shape[1], renv.data_ptr(),
+                                  n_fft, hop, int(bool(packed)), y.data_ptr(), _stream()), "jatts_gl_istft")
+    _count(2.0 * table.shape[0] * table.shape[1] * max(rb.total - rb.n_seq, 0))
+    return y
+
+
+def gl_exp(c, n_mels, scale, mean, log_base, ldo):
+    """jatts_gl_exp: base ** (c * scale + mean), f32 (rows, ldo), columns n_mels .. ldo - 1 zero.  ``log_base``: 0 (e), 2 or 10."""
+    lib = _abi.load()
+    _f32d("gl_exp", "contiguous float32 features (rows, >= n_mels) and statistics of n_mels", c, scale, mean, dims=(2, 1, 1))
+    if c.shape[1] < n_mels or scale.numel() != n_mels or mean.numel() != n_mels:
+        raise ValueError("gl_exp: contiguous float32 features (rows, >= n_mels) and statistics of n_mels expected")
+    out = torch.empty(c.shape[0], ldo, dtype=torch.float32, device=c.device)
+    _abi.check(lib.jatts_gl_exp(c.data_ptr(), c.shape[1], n_mels, c.shape[0], scale.data_ptr(), mean.data_ptr(), log_base, out.data_ptr(), ldo,
+                                _stream()), "jatts_gl_exp")
+    return out
+
+
+def gl_floor(lin, n_bins, eps, ldo):
+    """jatts_gl_floor: max(eps, lin), f32 (rows, ldo), columns n_bins .. ldo - 1 zero."""
+    lib = _abi.load()
+    _f32d("gl_floor", "a contiguous float32 (rows, >= n_bins) matrix", lin, dims=(2,))
+    out = torch.empty(lin.shape[0], ldo, dtype=torch.float32, device=lin.device)
+    _abi.check(lib.jatts_gl_floor(lin.data_ptr(), lin.shape[1], n_bins, lin.shape[0], float(eps), out.data_ptr(), ldo, _stream()), "jatts_gl_floor")
+    return out
+
+
+def gl_init(S, p0, n_fft, X):
+    """jatts_gl_init: X_0 = S * P0 into ``X`` f32 (rows, 2 * nbp).  ``p0``: complex64 (rows, n_bins), contiguous."""
+    lib = _abi.load()
+    _f32d("gl_init", "contiguous float32 device buffers", S, X, dims=(2, 2))
+    n_bins = n_fft // 2 + 1
+    if _dev(p0).dtype != torch.complex64 or not p0.is_contiguous() or tuple(p0.shape) != (S.shape[0], n_bins) or X.shape[0] < S.shape[0]:
+        raise ValueError("gl_init: contiguous complex64 phases (rows, n_bins) expected")
+    _abi.check(lib.jatts_gl_init(S.data_ptr(), S.shape[1], p0.data_ptr(), n_fft, S.shape[0], X.data_ptr(), X.shape[1], _stream()), "jatts_gl_init")
+    return X
+
+
 # ---- stage-1 pitch (csrc/pitch.hip; host layer: jatts_amd/features/pitch.py)
 def acf_from_mag(rb_frames, mag, table, out=None):
     """jatts_acf_from_mag: mag f32 (rows, ldm >= K) -> r f32 (rows, Lp), r[row][tau] = sum_k mag[row][k]^2 table[k][tau]; ``table``:

@@ -591,7 +591,7 @@ READ_KEYS = ("feat_list", "out_feat_type", "model_type", "model_params", "traine
 # ... and those that belong to stage 1 (preprocess) or stage 4 (tts_decode) and mean nothing to training
 OTHER_STAGE_KEYS = ("sampling_rate", "fft_size", "hop_size", "win_length", "window", "num_mels", "fmin", "fmax", "global_gain_scale", "log_base",
                     "pitch_extract_type", "pitch_extract_f0min", "pitch_extract_f0max", "energy_extract_type", "spkemb_checkpoint", "spkemb_params",
-                    "noise_scale")
+                    "noise_scale", "griffin_lim_iters")
 
 
 def unread_keys(config, cli_keys=()):
@@ -750,6 +750,22 @@ def _inference_kwargs(config):
     return {}
 
 
+def griffin_lim_fallback(config, stats, device):
+    """The vocoder of the intermediate waveforms for a config WITHOUT a ``vocoder:`` entry (the reference's tts_train.py:316-325): Griffin-Lim
+    (``vocoder.Spectrogram2Waveform``) where the config carries every analysis key it needs, as the recipe configs do; otherwise None and the
+    waveforms are skipped.  ``stats``: a {"mean", "scale"} dict or a callable that returns one (read only when it is needed)."""
+    import logging
+    from .vocoder.griffin_lim import CONFIG_KEYS
+    missing = [k for k in CONFIG_KEYS if k not in config]
+    if missing:
+        logging.info("No vocoder in the config: intermediate waveforms are skipped (no Griffin-Lim fallback).")
+        return None
+    from .vocoder import Spectrogram2Waveform
+    voc = Spectrogram2Waveform.from_config(config, stats() if callable(stats) else stats, device)
+    logging.info(f"No vocoder in the config: intermediate waveforms come from Griffin-Lim, {voc.gl.n_iter} iterations.")
+    return voc
+
+
 @torch.no_grad()
 def save_intermediate_results(trainer, batch, config, outdir, vocoder=None):
     """`_genearete_and_save_intermediate_result` (trainers/fastspeech2.py:102-223): up to ``num_save_intermediate_results`` utterances of a dev
@@ -767,7 +783,7 @@ def save_intermediate_results(trainer, batch, config, outdir, vocoder=None):
         plt = None
         logging.info("matplotlib is not importable: figures are skipped.")
     if vocoder is None:
-        logging.info("No vocoder: wav/<idx>_gen.wav is skipped (the reference's Griffin-Lim fallback is not part of this package).")
+        logging.info("No vocoder: wav/<idx>_gen.wav is skipped (the Griffin-Lim fallback needs the config's analysis keys: griffin_lim_fallback).")
     model, kw = trainer.model, _inference_kwargs(config)
     was = model.training
     model.eval()

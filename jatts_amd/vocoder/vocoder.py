@@ -73,6 +73,11 @@ class Vocoder(object):
             self._scale = (1.0 / self.stats["scale"]).contiguous()
             self._shift = (-self.stats["mean"] / self.stats["scale"]).contiguous()
 
+    @property
+    def hop(self):
+        """waveform samples per feature frame"""
+        return self.model.hop
+
     def set_precision(self, precision):
         self.model.set_precision(precision)
         return self
