@@ -781,7 +781,7 @@ def conv1d(rb, xs, w_packed, c_in, n_out, k_w, *, dtype, dil=1, pad=None, bias=N
     from pack_conv_weight_split (c_mult 64).  ``snake`` = (exp(alpha), 1 / (exp(beta) + 1e-9)) f32 vectors of n_out: the SnakeBeta
     activation (the ``snakebeta`` op) applied in the epilogue instead of ``act``.  ``split`` = (n_split, ld2, seq_col0): TWO outputs from one launch
     (the Q | K | V projection): channels < n_split row-major as usual, channels >= n_split transposed into a (n_out - n_split, ld2) matrix with the V^T
-    column layout ``seq_col0`` (RaggedBatch.vt_layout); returns (out, out2).  ``pad`` (default: the "same" offset (k_w - 1) // 2 * dil) must lie in
+    column layout ``seq_col0`` (RaggedBatch.vt_layout); returns (out, out2), fresh buffers or the caller's ``out=(out, out2)``.  ``pad`` (default: the "same" offset (k_w - 1) // 2 * dil) must lie in
     [0, (k_w - 1) * dil]; the library refuses anything else.  ``tap_window`` = (tap_group_n, tap_a0, tap_b0, tap_k): the caller's PROMISE that the weight
     is zero outside those taps (jatts_conv_desc.tap_group_n: a hint, same result with or without; check_tap_window verifies a dense weight)."""
     lib = _abi.load()
@@ -819,10 +819,18 @@ def conv1d(rb, xs, w_packed, c_in, n_out, k_w, *, dtype, dil=1, pad=None, bias=N
     out2 = None
     if split is not None:
         n_split, ld2, col2 = split
-        if transposed or out is not None or resid is not None or n_split % 256 or not 0 < n_split < n_out:
-            raise ValueError("conv1d: split takes a fresh row-major output, no residual, n_split a multiple of 256 below n_out")
-        out = torch.empty(rows, out_ld or n_split, dtype=odt, device=x0.device)
-        out2 = torch.empty(n_out - n_split, ld2, dtype=odt, device=x0.device)
+        pair = isinstance(out, (tuple, list))              # out=(out, out2): the caller's own buffers (the store tests prefill both with canaries)
+        if transposed or (out is not None and not pair) or resid is not None or n_split % 256 or not 0 < n_split < n_out:
+            raise ValueError("conv1d: split takes a fresh row-major output (or the pair out=(out, out2)), no residual, n_split a multiple of 256 below n_out")
+        if pair:
+            out, out2 = out
+            if out2.dtype != odt or not out2.is_contiguous() or out2.numel() < (n_out - n_split) * ld2:
+                raise ValueError("conv1d: split: out2 must be a contiguous (n_out - n_split, ld2) buffer of the output dtype")
+            if not out.is_contiguous() or out.numel() < rows * (out_ld or out.shape[-1]) or out_col0 + n_split > (out_ld or out.shape[-1]):
+                raise ValueError("conv1d: split: out must hold rows x out_ld elements with the n_split-wide window inside a row")
+        else:
+            out = torch.empty(rows, out_ld or n_split, dtype=odt, device=x0.device)
+            out2 = torch.empty(n_out - n_split, ld2, dtype=odt, device=x0.device)
     if out is None:
         if transposed:
             # slack columns of an aligned V^T layout stay uninitialised: the attention kernel masks every element
